@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""bench.py -- BASELINE.json's headline metric on MI355X, plus BASELINE's other
-GPU configurations as sub-objects of the same JSON line.
+"""bench.py -- BASELINE.json's headline metric on MI355X; with --full, plus
+BASELINE's other GPU configurations as sub-objects of the same JSON line.
 
 metric : demod Msymbols/s (batch) + achieved HBM GB/s, QPSK@9600/96kHz
 workload (N=1): BASELINE configs[1] -- QPSK @ 9600 sym/s, 96 kHz, batch 4096
@@ -17,13 +17,20 @@ step   : one pass of the whole demod path over ONE batch: band-pass filtfilt
 scaling: weak for qpsk9600 / fsk9600 (every rank its own batch), strong for
           ofdm8 / psk8fec (a global batch of 8192 sharded over the ranks).
 
-Also reported: the one-batch-at-a-time latency, per-kernel HIP-event times
-(in flight and solo), the roofline (contract form + solo + pipeline + FP64),
-the CPU baseline (the C oracle on the host cores), bit-exact parity of
-sampled streams of in-flight slots against the oracle, and for N>1 a check
-that the gathered buffer equals every rank's own output.
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`value`, `ms_per_step`, the in-flight per-kernel HIP-event times); with
+--dump-outputs DIR it also writes what the last timed step returned as
+DIR/<name>.npy (the inputs are seeded: the same arguments give the same files).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--inflight P]
+With --full, also reported after the timed steps: the one-batch-at-a-time
+latency, per-kernel HIP-event times solo, the roofline (contract form + solo
++ pipeline + FP64), the CPU baseline (the C oracle on the host cores),
+bit-exact parity of sampled streams of in-flight slots against the oracle,
+the sustained run, the host and drop-in paths, the other workloads, and for
+N>1 a check that the gathered buffer equals every rank's own output.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--inflight P] [--full]
+                        [--dump-outputs DIR]
         multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
         (the launcher only starts the ranks: bootstrap, barriers and gathers
         are multi.py's -- a file store and RCCL, no torch in the process)
@@ -335,10 +342,26 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
     value = B_global * sym_per_stream / (dt / K) / 1e6
     kavg = {k: v / max(1, nt[0]) for k, v in kt.items() if v > 0}
 
+    # ---- --dump-outputs: what the last timed step's caller received ------------
+    dumped = None
+    if headline and args.dump_outputs and rank == 0:
+        c = ctx[(n_launch - 1) % P]
+        rows = launch_sizes[-1]                          # (the last launch may hold fewer steps)
+        bufs = {"bytes": (c["out"], cap, np.uint8), "lengths": (c["len"], 1, np.int64),
+                "sync_idx": (c["sync"], 1, np.int64)}
+        if fec_fused:
+            bufs.update(fec_bytes=(c["fec"], cap, np.uint8), fec_lengths=(c["flen"], 1, np.int64),
+                        fec_ok=(c["ok"], 1, np.int32))
+        host = {}
+        for k, (d, w, dt_) in bufs.items():
+            host[k] = np.empty((rows, w) if w > 1 else rows, dt_)
+            _amr.check(L.amr_memcpy_d2h(_amr.ptr(host[k]), d, host[k].nbytes))
+        dumped = dump_outputs(args.dump_outputs, host, {"bytes": "lengths", "fec_bytes": "fec_lengths"})
+
     # ---- sustained: the same pipeline for about --sustain-seconds (headline
     # only, after the timed region; a longer run settles at a lower clock) ----
     sustained = None
-    if headline and args.sustain_seconds > 0:
+    if headline and args.full and args.sustain_seconds > 0:
         n_s = max(P, int(round(args.sustain_seconds / max(1e-4, dt / n_launch) / P)) * P)
         barrier(tp)
         _amr.check(L.amr_device_synchronize())
@@ -356,7 +379,7 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
     # a plan without the in-flight hint picks the latency layout (row kernels,
     # DESIGN.md §3.2); its bytes must equal the lane layout's on the same input
     lat1 = None
-    if headline and not fsk and not args.no_latency:
+    if headline and args.full and not fsk and not args.no_latency:
         lp = _amr.PskPlan("qpsk", N, baud, 3000.0, FS, max_streams=B, device=dev)
         lo_, ll_, ls_ = mem.alloc(B * cap), mem.alloc(B * 8), mem.alloc(B * 8)
         ts = []
@@ -380,7 +403,7 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
     # (a slot whose last launch was partial keeps, past it, its previous
     # launch's rows of the same input)
     outs = []
-    for c in ctx:
+    for c in ctx if args.full else ():
         o = np.empty((BL, cap), np.uint8)
         ln = np.empty(BL, np.int64)
         sy = np.empty(BL, np.int64)
@@ -392,7 +415,7 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
 
     # ---- N>1: the gathered buffer must equal every rank's own output ----------
     gather_check = None
-    if comm is not None:
+    if comm is not None and args.full:
         last = (n_launch - 1) % P
         o, ln, sy = outs[last]
         gp = np.empty((world, R, cap), np.uint8)
@@ -414,7 +437,7 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
     # ---- parity: sampled streams of in-flight slots vs the oracle; CPU baseline
     result = None
     host_res = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import oracle
         # the CPU baseline runs on every core this process may use (its
         # affinity mask, within its cgroup CPU quota: the GPU box's host cores
@@ -670,6 +693,21 @@ def run_workload(name, args, tp, world, rank, dev, comm, headline):
         result["exact_probe"] = fsk_exact_probe(N, baud, mark, space, dev)
     if result is not None and fsk_one is not None:
         result["dropin"] = fsk_dropin_path(*fsk_one, baud, mark, space)
+    if rank == 0 and not args.full:
+        # the plain run's line: the headline figure and what the timed region itself measured
+        result = {
+            "metric": W["metric"], "value": round(value, 3), "unit": "Msym/s", "n_gpus": world, "steps": K,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": name, "global_batch": B_global, "samples_per_stream": N,
+                       "symbols_per_stream": sym_per_stream, "batches_in_flight": P, "steps_per_launch": C,
+                       "streams_per_launch": BL, "kernel_layout": layout,
+                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))},
+            "latency_ms_per_global_batch": round(float(np.mean(launch_ms)), 3) if launch_ms else None,
+            "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
+        }
+    if result is not None and dumped is not None:
+        result["dumped_outputs"] = dumped
     return result
 
 
@@ -1085,6 +1123,36 @@ def host_path(L, fsk, xh, B, N, baud, mark, space, dev, cap, sym_per_stream, out
     return res
 
 
+DUMP_BUDGET = 48 * 1000 * 1000  # bytes of .npy data per --dump-outputs folder (kept well under 64 MB)
+
+
+def dump_outputs(path, host, lengths_of, budget=DUMP_BUDGET):
+    """Write the arrays of `host` (name -> one row per stream, all with the
+    same number of rows) as path/<name>.npy: integers up to 32 bits as
+    float32, 64-bit ones as float64 (both exact for the values the path
+    writes).  Of a byte matrix named in `lengths_of`, only the bytes below the
+    stream's length (the array named there) are output; the rest of the
+    row is written as 0.  When the arrays exceed `budget` bytes, the same
+    fixed, seeded sample of rows is taken of every array; rows.npy holds the
+    row numbers written.  Returns {file name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(host.values())))
+    as_f = {k: np.float64 if v.dtype.itemsize > 4 else np.float32 for k, v in host.items()}
+    per_row = sum(int(np.prod(v.shape[1:], dtype=np.int64)) * np.dtype(as_f[k]).itemsize for k, v in host.items()) + 8
+    keep = np.arange(n)
+    if n * per_row > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, budget // per_row), replace=False))
+    written = {}
+    for k, v in {**host, "rows": keep}.items():
+        a = v if k == "rows" else v[keep]
+        if k in lengths_of:
+            a = np.where(np.arange(a.shape[1])[None, :] < host[lengths_of[k]][keep][:, None], a, 0)
+        a = a.astype(as_f.get(k, np.float64))
+        np.save(os.path.join(path, k + ".npy"), a)
+        written[k + ".npy"] = list(a.shape)
+    return written
+
+
 def launch_plan(K, B, strong, coalesce=0):
     """(C, BL, n_launch, streams of each launch) for K timed steps of B
     streams per rank: a strong-scaling shard too small to fill the GPU alone
@@ -1115,11 +1183,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this benchmark measures and checks: the "
+                         "sustained run, one-batch latency, oracle parity, the CPU baseline, the roofline, the host "
+                         "and drop-in paths and, for qpsk9600, the other workloads; without it a run only sets up, "
+                         "warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (decoded bytes, lengths, "
+                         "sync indices of its streams) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--sub-steps", type=int, default=64,
-                    help="timed steps of each sub-workload of the default run (fsk9600, ofdm8, psk8fec)")
+                    help="timed steps of each sub-workload of a --full run (fsk9600, ofdm8, psk8fec)")
     ap.add_argument("--workload", choices=list(WORKLOADS), default="qpsk9600",
-                    help="the headline; qpsk9600 (BASELINE configs[1]) also reports the other configs as sub-objects")
-    ap.add_argument("--no-sub", action="store_true", help="skip the sub-workloads of the default run")
+                    help="the headline; qpsk9600 (BASELINE configs[1]) with --full also reports the other configs as "
+                             "sub-objects")
+    ap.add_argument("--no-sub", action="store_true", help="skip the sub-workloads of a --full run")
     ap.add_argument("--batch", type=int, default=0,
                     help="streams per GPU (qpsk9600/fsk9600, default 4096/16384) or in total (ofdm8/psk8fec, 8192)")
     ap.add_argument("--samples", type=int, default=96000)
@@ -1159,7 +1236,7 @@ def main():
     comm = tp.comm if tp is not None else None
 
     result = run_workload(args.workload, args, tp, world, rank, dev, comm, headline=True)
-    if args.workload == "qpsk9600" and not args.no_sub and not args.batch:
+    if args.full and args.workload == "qpsk9600" and not args.no_sub and not args.batch:
         subs = {}
         for name in ("fsk9600", "ofdm8", "psk8fec"):
             r = run_workload(name, args, tp, world, rank, dev, comm, headline=False)
@@ -1176,6 +1253,7 @@ def main():
             result["workloads"] = subs
     if rank == 0 and result is not None:
         result["build_id"] = L.amr_build_id().decode()
+        result["full"] = args.full
         print(json.dumps(result), flush=True)
     if tp is not None:
         tp.close()

@@ -19,7 +19,7 @@ for r in $(seq ${REPS:-2}); do
   for v in "${VARS[@]}"; do
     e="${v%%|*}"; a="${v#*|}"; i=$((i + 1))
     out=gpurun_out/ab_${TAG}_${r}_$i.json
-    env $e timeout -k 10 300 python -u bench.py --no-host-path --no-dropin --cpu-seconds 0 $a > $out 2> ${out%.json}.err || { echo "fail: $v"; exit 1; }
+    env $e timeout -k 10 300 python -u bench.py --full --no-host-path --no-dropin --cpu-seconds 0 $a > $out 2> ${out%.json}.err || { echo "fail: $v"; exit 1; }
     python - "$out" "$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

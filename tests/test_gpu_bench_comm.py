@@ -33,7 +33,7 @@ def test_force_comm_gather_check(extra):
     subprocess.run([sys.executable, "-c", "import torch"], timeout=400, check=True)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--force-comm", "--steps", "4", "--warmup", "1", "--no-sub", "--no-host-path", "--no-latency",
+           "--full", "--force-comm", "--steps", "4", "--warmup", "1", "--no-sub", "--no-host-path", "--no-latency",
            "--no-dropin", "--sustain-seconds", "0", "--cpu-seconds", "0", "--samples", "24000", *extra]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
