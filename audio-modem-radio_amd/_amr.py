@@ -63,10 +63,18 @@ EXPORTS = [
     "amr_psk_demod_host_edges", "amr_psk_demod_device_edges", "amr_fsk_demod_host_edges", "amr_fsk_demod_device_edges",
     "amr_psk_split_bounds_host", "amr_psk_plan_set_split_strict", "amr_psk_plan_split_strict",
     "amr_psk_plan_last_strict", "amr_psk_split_strict_design",
+    "amr_hell_pixels", "amr_hell_work_bytes", "amr_hell_demod_host", "amr_hell_demod_device", "amr_hell_glyph_rows",
 ]
 
-TX_BPSK, TX_QPSK, TX_FSK = 0, 1, 2
-TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK}
+TX_BPSK, TX_QPSK, TX_FSK, TX_HELL = 0, 1, 2, 3
+TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL}
+
+# AMR_HELL_ELEM_* (include/amr.h): the element types the Hellschreiber receiver reads
+HELL_PCM16 = 11
+HELL_ELEMS = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.float16): 2,
+              np.dtype(np.int8): 3, np.dtype(np.int16): 4, np.dtype(np.int32): 5, np.dtype(np.int64): 6,
+              np.dtype(np.uint8): 7, np.dtype(np.uint16): 8, np.dtype(np.uint32): 9, np.dtype(np.uint64): 10}
+HELL_BLANK = 255                                       # payload index of a character outside the glyph table
 
 
 def tx_samples(mode: int, n_bytes: int, baud, samp_rate) -> int:
@@ -83,7 +91,76 @@ def _raise_tx(rc: int):
         raise ValueError(msg)                      # numpy's error, modem.py:58-61 / 181-183
     if msg == "float division by zero":
         raise ZeroDivisionError(msg)
+    if msg.startswith(("zero-size array", "negative dimensions", "range() arg 3")):
+        raise ValueError(msg)                      # numpy's / range()'s error, hellschreiber.py:137, 148, 162
     raise AmrError(rc, msg)
+
+
+def hell_glyph_rows() -> np.ndarray:
+    """The glyph bitmaps libamr.so carries: [95][7] uint8 for ' '..'~' (byte r =
+    pixel row r, bit i = the row's i-th pixel on the air).  Host only."""
+    rows = np.zeros((95, 7), np.uint8)
+    lib().amr_hell_glyph_rows(ptr(rows), None)
+    return rows
+
+
+def hell_rx_lookup() -> bytes:
+    """The receiver's 128-entry lookup (7-pixel value -> character).  Host only."""
+    lut = np.zeros(128, np.uint8)
+    lib().amr_hell_glyph_rows(None, ptr(lut))
+    return lut.tobytes()
+
+
+def hell_payload(text: str) -> bytes:
+    """One glyph index per character of `text` (AMR_TX_HELL's payload)."""
+    return bytes(ord(c) - 0x20 if 0x20 <= ord(c) <= 0x7E else HELL_BLANK for c in text)
+
+
+def hell_elem(dtype) -> int:
+    """AMR_HELL_ELEM_* for a raw capture's dtype; TypeError (naming it) for one
+    numpy's arithmetic cannot be restated for (longdouble, complex, object ...)."""
+    dt = np.dtype(dtype)
+    if dt.kind == "b":
+        dt = np.dtype(np.int8)                         # bool ** 2 is int8
+    e = HELL_ELEMS.get(dt.newbyteorder("=") if dt.kind in "iuf" else dt)
+    if e is None:
+        raise TypeError(f"feld_hell_demodulate: unsupported sample dtype {np.dtype(dtype)}")
+    return e
+
+
+def hell_demod(x: np.ndarray, baud, samp_rate, elem=None, energy=False):
+    """hellschreiber_demodulate of every row of x [B][N] on the GPU
+    (amr_hell_demod_host): list of bytes; with energy=True also the pixels'
+    np.mean(chunk ** 2) values [B][pixels] widened to float64.  elem: an
+    AMR_HELL_ELEM_* override (HELL_PCM16 for int16 PCM); default from x.dtype."""
+    if elem is None:
+        elem = hell_elem(x.dtype)
+    if x.dtype.kind == "b":
+        x = x.astype(np.int8)
+    if not x.dtype.isnative:
+        x = x.astype(x.dtype.newbyteorder("="))
+    if x.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    B, n = x.shape
+    if x.strides[1] != x.itemsize or (B > 1 and (x.strides[0] % x.itemsize or x.strides[0] < n * x.itemsize)):
+        x = np.ascontiguousarray(x)                    # rows of a wider array go as they are (x_stride)
+    stride = x.strides[0] // x.itemsize if B > 1 else n
+    n_pix = int(lib().amr_hell_pixels(n, float(baud), float(samp_rate)))
+    if n_pix < 0:
+        _raise_tx(n_pix)
+    if B == 0:
+        return ([], np.zeros((0, n_pix))) if energy else []
+    require_gpu()
+    check(lib().amr_set_device(default_device()))
+    cap = max(1, n_pix // 7)
+    out = np.zeros((B, cap), np.uint8)
+    ln = np.zeros(B, np.int64)
+    en = np.zeros((B, n_pix), np.float64) if energy else None
+    rc = lib().amr_hell_demod_host(ptr(x), int(elem), B, stride, n, float(baud), float(samp_rate), ptr(out), cap, ptr(ln), ptr(en) if energy else None)
+    if rc != AMR_OK:
+        _raise_tx(rc)
+    outs = [out[i, :ln[i]].tobytes() for i in range(B)]
+    return (outs, en) if energy else outs
 
 
 def modulate(mode: int, datas, baud, f0, f1=0.0, samp_rate=96000, n_out=None, pcm=False):
@@ -288,6 +365,11 @@ def lib():
             "amr_tx_work_bytes": (I64, [I32, D, D, I64, I64]),
             "amr_modulate_host": (I32, [I32, D, D, D, D, P, I64, P, I64, P, I64, I64, P, I64]),
             "amr_modulate_device": (I32, [P, I32, D, D, D, D, P, I64, P, I64, P, I64, I64, P, I64, P, I64]),
+            "amr_hell_pixels": (I64, [I64, D, D]),
+            "amr_hell_work_bytes": (I64, [D, D]),
+            "amr_hell_demod_host": (I32, [P, I32, I64, I64, I64, D, D, P, I64, P, P]),
+            "amr_hell_demod_device": (I32, [P, P, I32, I64, I64, I64, D, D, P, I64, P, P, P, I64]),
+            "amr_hell_glyph_rows": (I32, [P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)

@@ -7,6 +7,7 @@
 //   ramp = int(len(symbol) * 0.1)                 modem.py:58, 180
 //   spb  = int(round(samp_rate * (1.0 / baud)))   modem.py:271-272 (round half even)
 //   inc  = 2 * np.pi * f * (spb / samp_rate)      modem.py:292
+//   spp  = int(round(samp_rate / baud))           hellschreiber.py:135 (AMR_TX_HELL: samples per pixel)
 // and the reference's error contract for them.  The sample work is
 // tx_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -33,13 +34,14 @@ constexpr double kPi = 3.141592653589793;   // np.pi
 int64_t tx_symbols(int mode, int64_t nb) {
   if (mode == AMR_TX_QPSK) return 40 + 4 * nb;
   if (mode == AMR_TX_BPSK) return 80 + 8 * nb;
+  if (mode == AMR_TX_HELL) return 105 + 51 * nb;             // pixels: 70 + 51 per character + 35
   return 8 * (4 + nb);
 }
 
 // samples per symbol as the reference computes it; an AMR_E_* code (< 0 with
 // the message set) when the reference raises for these parameters
 int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_out, TxParams* p) {
-  if (mode != AMR_TX_BPSK && mode != AMR_TX_QPSK && mode != AMR_TX_FSK)
+  if (mode != AMR_TX_BPSK && mode != AMR_TX_QPSK && mode != AMR_TX_FSK && mode != AMR_TX_HELL)
     return fail(AMR_E_INVALID, "unknown modulation mode");
   if (baud == 0.0) return fail(AMR_E_INVALID, "float division by zero");
   if (!std::isfinite(baud) || !std::isfinite(fs)) return fail(AMR_E_INVALID, "baud and sample_rate must be finite");
@@ -47,7 +49,16 @@ int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_o
   p->mode = mode;
   p->fs = fs;
   p->n_out = n_out;
-  if (mode == AMR_TX_FSK) {
+  if (mode == AMR_TX_HELL) {
+    const double spp = std::nearbyint(fs / baud);            // int(round(samp_rate / baud))
+    if (!(std::fabs(spp) < 2147483648.0)) return fail(AMR_E_INVALID, "samples per pixel out of range (>= 2^31)");
+    if (spp < 0) return fail(AMR_E_INVALID, "negative dimensions are not allowed");   // np.zeros(total_samples)
+    if (spp == 0)                                            // np.max of the empty waveform
+      return fail(AMR_E_INVALID, "zero-size array to reduction operation maximum which has no identity");
+    p->sps = (int64_t)spp;
+    p->c0 = 2.0 * kPi * f0;                                  // 2 * math.pi * carrier (* t on the device)
+    p->c1 = p->c0;
+  } else if (mode == AMR_TX_FSK) {
     const double spb = std::nearbyint(fs * (1.0 / baud));   // int(round(samp_rate * bit_dur))
     p->sps = spb > 0 ? (int64_t)spb : 0;
     p->c0 = 2.0 * kPi * f0;

@@ -5,6 +5,7 @@
 //   qpsk_modulate   /root/reference/modem.py:138-186  DQPSK, Gray dibit steps
 //   fsk_modulate    /root/reference/modem.py:270-295  CPFSK, phase mod 2*pi
 //   wav_from_array  /root/reference/modem.py:360-368  int16(arr * 32767)
+//   hellschreiber_modulate  hellschreiber.py:109-152  (AMR_TX_HELL, below)
 //
 // Three launches per call:
 //   T0 k_tx_tables  the per-symbol tables the reference rebuilds per symbol:
@@ -28,6 +29,7 @@
 
 #include "amr_internal.h"
 #include "amr.h"
+#include "hell_glyphs.h"
 
 namespace amr {
 
@@ -240,6 +242,114 @@ __global__ __launch_bounds__(256) void k_tx_synth(const uint8_t* __restrict__ da
   }
 }
 
+// ---- AMR_TX_HELL: hellschreiber_modulate (hellschreiber.py:109-152) ----
+// The payload is one glyph index per character (0..94 = ' '..'~', kHellBlank
+// for a character outside the table: the host did the UTF-8 decode).  Pixels:
+// 70 ones, per character 7 rows x 7 bits LSB first + 2 zeros (a blank cell: 51
+// zeros), 35 ones.  Every on-pixel is the same sps samples, so two launches:
+//   k_hell_tab   tab[j] = float32(sin(((2*pi)*carrier) * (j / fs))), then the
+//                reference's normalisation of the whole waveform, whose peak is
+//                the table's: m = max |tab| (float32), tab = tab / m * 0.8 (a
+//                float32 divide, then a float32 multiply), skipped unless m > 0
+//                (carrier 0, or a NaN, which np.max propagates).  One block.
+//   k_hell_fill  4 samples per thread: out = pixel bit ? tab[k % sps] : 0.
+__constant__ uint8_t c_tx_glyphs[kHellGlyphs][kHellRows] = {AMR_HELL_GLYPH_TABLE};
+
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
+
+__global__ __launch_bounds__(1024) void k_hell_tab(TxParams p, float* __restrict__ tab) {
+  __shared__ float red[1024];
+  float mx = 0.0f;
+  for (int64_t j = threadIdx.x; j < p.sps; j += 1024) {
+    const double t = (double)j / p.fs;             // np.arange(sps) / samp_rate
+    const float v = (float)sin(p.c0 * t);          // out[start:end] = np.sin(2 * pi * carrier * t)
+    tab[j] = v;
+    mx = nan_max(mx, fabsf(v));
+  }
+  red[threadIdx.x] = mx;
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + h]);
+    __syncthreads();
+  }
+  const float m = red[0];                          // np.max(np.abs(out))
+  if (!(m > 0.0f)) return;
+  for (int64_t j = threadIdx.x; j < p.sps; j += 1024) {   // each thread rewrites only what it wrote
+    const float q = tab[j] / m;                    // out / m
+    tab[j] = q * 0.8f;                             // ... * 0.8 (float32, NEP 50)
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_hell_fill(const uint8_t* __restrict__ data, int64_t stride,
+                                                   const int64_t* __restrict__ n_bytes, TxParams p,
+                                                   const float* __restrict__ tab, float* __restrict__ out,
+                                                   int64_t out_stride, int16_t* __restrict__ pcm,
+                                                   int64_t pcm_stride) {
+  const int64_t s = blockIdx.y;
+  int64_t nc = n_bytes[s];
+  nc = nc < 0 ? 0 : (nc > stride ? stride : nc);
+  const int64_t n_pix = 105 + 51 * nc;             // 70 + 51 per character + 35
+  const uint8_t* __restrict__ d = data + s * stride;
+  const int64_t k0 = (int64_t)blockIdx.x * 1024 + 4 * threadIdx.x;
+  if (k0 >= p.n_out) return;
+  int64_t pix = k0 / p.sps;
+  int64_t j = k0 - pix * p.sps;
+  float f[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    bool on = false;
+    if (pix < 70) {
+      on = true;
+    } else if (pix < n_pix - 35) {
+      const int64_t q = pix - 70;
+      const int64_t c = q / 51;                    // c < nc <= stride
+      const int r = (int)(q - c * 51);
+      const uint32_t g = d[c];
+      if (g < (uint32_t)kHellGlyphs && r < 49) on = (c_tx_glyphs[g][r / 7] >> (r % 7)) & 1;
+    } else if (pix < n_pix) {
+      on = true;
+    }
+    f[u] = on ? tab[j] : 0.0f;
+    if (++j == p.sps) {
+      j = 0;
+      ++pix;
+    }
+  }
+  int16_t q[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) q[u] = (int16_t)(int)(f[u] * 32767.0f);   // (arr * 32767).astype(np.int16)
+  float* __restrict__ o = out + s * out_stride + k0;
+  int16_t* __restrict__ c = pcm ? pcm + s * pcm_stride + k0 : nullptr;
+  if (VEC && k0 + 4 <= p.n_out) {
+    *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
+    if (c) *reinterpret_cast<short4*>(c) = make_short4(q[0], q[1], q[2], q[3]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (k0 + u < p.n_out) {
+        o[u] = f[u];
+        if (c) c[u] = q[u];
+      }
+    }
+  }
+}
+
+static void launch_tx_hell(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
+                           int64_t n_streams, float* tab, float* out, int64_t out_stride, int16_t* pcm,
+                           int64_t pcm_stride, hipStream_t st) {
+  hipLaunchKernelGGL(k_hell_tab, dim3(1), dim3(1024), 0, st, p, tab);
+  const dim3 sg((unsigned)((p.n_out + 1023) / 1024), (unsigned)n_streams);
+  const bool vec = (out_stride % 4) == 0 && ((uintptr_t)out % 16) == 0 &&
+                   (!pcm || ((pcm_stride % 4) == 0 && ((uintptr_t)pcm % 8) == 0));
+  if (vec)
+    hipLaunchKernelGGL((k_hell_fill<true>), sg, dim3(256), 0, st, data, stride, n_bytes, p, tab, out, out_stride, pcm,
+                       pcm_stride);
+  else
+    hipLaunchKernelGGL((k_hell_fill<false>), sg, dim3(256), 0, st, data, stride, n_bytes, p, tab, out, out_stride, pcm,
+                       pcm_stride);
+}
+
 template <int MODE>
 static void launch_tx_mode(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
                            int64_t n_streams, const double* tab, double* phase, float* out, int64_t out_stride,
@@ -266,6 +376,10 @@ hipError_t launch_tx(const TxParams& p, const uint8_t* data, int64_t stride, con
                      int64_t n_streams, double* work, float* out, int64_t out_stride, int16_t* pcm,
                      int64_t pcm_stride, hipStream_t st) {
   if (n_streams <= 0 || p.n_out <= 0) return hipSuccess;
+  if (p.mode == AMR_TX_HELL) {
+    launch_tx_hell(p, data, stride, n_bytes, n_streams, (float*)work, out, out_stride, pcm, pcm_stride, st);
+    return hipGetLastError();
+  }
   double* tab = work;
   double* phase = work + ((3 * p.sps + 1) & ~(int64_t)1);   // 16-B aligned rows (sym_stride is even)
   hipLaunchKernelGGL(k_tx_tables, dim3((unsigned)((p.sps + 255) / 256)), dim3(256), 0, st, p, tab);

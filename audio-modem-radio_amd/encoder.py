@@ -20,9 +20,10 @@ Reference map (encoder.py):
   get_encoding_stats                          :309-315
   verify_audio_output                         :318-348
 Differences: CACHE_DIR is created when the first WAV is written, not at import
-(the reference runs os.makedirs at import, encoder.py:20-21); HELLSCHREIBER
-(hellschreiber.py) is outside this build's scope and raises
-NotImplementedError.  The reference's modulator calls are kept as written, so
+(the reference runs os.makedirs at import, encoder.py:20-21).  HELLSCHREIBER
+modulates framed.decode('utf-8') with the reference's defaults (encoder.py:196;
+the strict decode's UnicodeDecodeError on a binary frame is the reference's
+too).  The reference's modulator calls are kept as written, so
 the ones that pass keywords the aliases do not take (8PSK, APSK16, DSSS, MSK,
 FT8, PSK31, FELD_HELL in encode_file_parts) raise the same TypeError here.
 """
@@ -159,7 +160,7 @@ _PART_CALLS = {
 
 def _modulate_part(framed: bytes, mode: str, symbol_rate: int) -> np.ndarray:
     if mode == "HELLSCHREIBER":
-        raise NotImplementedError("Hellschreiber (hellschreiber.py) is outside this build's scope (SURVEY §2)")
+        return modem.hellschreiber_modulate(framed.decode('utf-8'))       # encoder.py:196
     if mode not in _PART_CALLS:
         raise ValueError(f"Modo desconhecido: {mode}")
     fn, kw = _PART_CALLS[mode]

@@ -18,6 +18,12 @@ Transmit side (on the GPU: tx_kernels.hip):
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
   samples equal the reference's up to the last-ulp sin difference the tests bound.
   wav_from_array modem.py:360-368 (host WAV writer).
+
+Hellschreiber (hellschreiber.py, modem.py:400-403), both directions on the GPU:
+  feld_hell_demodulate (+ feld_hell_demodulate_batch)  hell_kernels.hip: the
+  per-pixel np.mean(chunk ** 2) > 0.1 in numpy's summation order and dtypes,
+  bit for bit, then the 7-pixel glyph lookup;
+  feld_hell_modulate / hellschreiber_modulate / modulate_batch("hell", ...).
 """
 from __future__ import annotations
 
@@ -197,12 +203,61 @@ def psk31_demodulate(s, b, c, sr=96000):
     return bpsk_demodulate(s, 31.25, c, sr)
 
 
+# ---------------------------------------------------------------------------
+# Hellschreiber (hellschreiber.py; modem.py:400-403): a per-pixel energy
+# detector + 7-pixel glyph lookup on receive (hell_kernels.hip, numpy's own
+# summation order and dtypes, so the decisions are np.mean(chunk ** 2) > 0.1's
+# bit for bit), on/off keyed glyph pixels on transmit (tx_kernels.hip).
+def _hell_sps(baud, samp_rate, tx=False) -> int:
+    """hellschreiber.py:135, 158 -- with Python's own exceptions for a zero /
+    non-finite baud (ZeroDivisionError, OverflowError, ValueError); tx: also
+    numpy's ValueError for a waveform of <= 0 samples per pixel (host
+    arithmetic in libamr.so, before any device work)."""
+    sps = int(round(samp_rate / baud))
+    if tx:
+        _amr.tx_samples(_amr.TX_HELL, 0, baud, samp_rate)
+    return sps
+
+
+def hellschreiber_modulate(text: str, baud=122.5, carrier=1000.0, samp_rate=SAMPLE_RATE) -> np.ndarray:
+    """hellschreiber.py:109-152: 70 sync pixels, per character 7 x 7 glyph bits +
+    2 blank (51 blank for a character outside the map), 35 end pixels; each
+    on-pixel a carrier burst, the whole normalised to 0.8."""
+    _hell_sps(baud, samp_rate, tx=True)
+    return _amr.modulate(_amr.TX_HELL, [_amr.hell_payload(text)], baud, carrier, 0.0, samp_rate)[0]
+
+
 def feld_hell_modulate(d, b, c, s=96000):
-    raise NotImplementedError("Hellschreiber (hellschreiber.py) is outside this build's scope (SURVEY §2)")
+    return hellschreiber_modulate(d.decode('utf-8', 'ignore'), b, c, s)
+
+
+def _hell_batch(x2d: np.ndarray, baud, samp_rate, elem=None) -> list:
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    elem = _amr.hell_elem(x2d.dtype) if elem is None else elem      # TypeError names an unsupported dtype
+    if _hell_sps(baud, samp_rate) < 0 and x2d.shape[0] > 0:         # range() with a negative step: nothing decoded
+        return [b""] * x2d.shape[0]
+    return _amr.hell_demod(x2d, baud, samp_rate, elem)
 
 
 def feld_hell_demodulate(s, b, c, sr=96000):
-    raise NotImplementedError("Hellschreiber (hellschreiber.py) is outside this build's scope (SURVEY §2)")
+    """hellschreiber_demodulate(s, b, c, sr).encode('utf-8') (modem.py:403;
+    the carrier is unused there too), on the GPU."""
+    x = np.asarray(s)
+    if x.ndim != 1:
+        raise ValueError("feld_hell_demodulate expects a 1-D sample array (use feld_hell_demodulate_batch)")
+    return _hell_batch(x[None, :], b, sr)[0]
+
+
+def feld_hell_demodulate_batch(samples: np.ndarray, baud=122.5, carrier=1000.0, samp_rate=96000) -> list:
+    """[B, N] equal-length captures -> B bytes objects (each == feld_hell_demodulate(row))."""
+    return _hell_batch(np.asarray(samples), baud, samp_rate)
+
+
+def _pcm16_hell(pcm: np.ndarray, baud=122.5, carrier=1000.0, samp_rate=96000) -> bytes:
+    """16-bit WAV samples as pcm / 32768 in float64 (decoder._Pcm16), converted on the device."""
+    x = np.ascontiguousarray(pcm, np.int16)[None, :]
+    return _hell_batch(x, baud, samp_rate, elem=_amr.HELL_PCM16)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -227,8 +282,15 @@ def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=9600
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
     cut / zero-padded to n_out; default the longest), plus wav_from_array's
     int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' (f0 = carrier) or
-    'fsk' (f0 = mark_freq, f1 = space_freq)."""
+    'fsk' (f0 = mark_freq, f1 = space_freq), or 'hell' (datas: texts or UTF-8
+    bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
+    pass baud=122.5 for the reference's default)."""
     mode = _amr.TX_MODES[kind]
+    if kind == "hell":
+        _hell_sps(baud, samp_rate, tx=True)
+        texts = [d if isinstance(d, str) else bytes(d).decode('utf-8', 'ignore') for d in datas]
+        return _amr.modulate(mode, [_amr.hell_payload(t) for t in texts], baud, 1000.0 if f0 is None else f0, 0.0,
+                             samp_rate, n_out, pcm)
     if f0 is None:
         f0 = 1200.0 if kind == "fsk" else 3000.0
     if f1 is None:

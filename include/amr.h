@@ -39,6 +39,9 @@
  *   amr_modulate_host       modem.bpsk_modulate / qpsk_modulate / fsk_modulate
  *                           (modem.py:28-65, 138-186, 270-295) + the int16 of
  *                           wav_from_array (modem.py:360-368), batched
+ *   amr_hell_demod_host     hellschreiber.hellschreiber_demodulate
+ *                           (hellschreiber.py:155-187), batched; AMR_TX_HELL is
+ *                           hellschreiber_modulate (hellschreiber.py:109-152)
  *   amr_allgather           the gather of decoded bytes across GPUs (RCCL)
  *
  * Status: every function returns AMR_OK (0) or a negative AMR_E_* code;
@@ -73,7 +76,10 @@ extern "C" {
                                   caller's dtype forms it); the PSK split's strict mode
                                   (amr_psk_plan_set_split_strict ...); F2's margin from a standard
                                   FFT rounding bound (amr_fsk_fft_margin, amr_fsk_plan_margin); the FSK
-                                  split's strict mode (amr_fsk_plan_set_split_strict ...) */
+                                  split's strict mode (amr_fsk_plan_set_split_strict ...)
+                                  additions under 5 (nothing existing changed): the Hellschreiber
+                                  receiver (amr_hell_pixels, amr_hell_work_bytes, amr_hell_demod_host /
+                                  _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -530,6 +536,13 @@ int amr_frame_parse_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_s
 #define AMR_TX_BPSK 0              /* bpsk_modulate  modem.py:28-65   */
 #define AMR_TX_QPSK 1              /* qpsk_modulate  modem.py:138-186 */
 #define AMR_TX_FSK 2               /* fsk_modulate   modem.py:270-295 */
+/* hellschreiber_modulate (hellschreiber.py:109-152).  The payload is one glyph
+ * index per character: 0..94 for ' '..'~', 255 for a character outside the
+ * table (a blank 51-pixel cell); the caller decodes the text.  f0 = carrier.
+ * baud / sample_rate rounding to 0 samples per pixel is the reference's
+ * ValueError (np.max of an empty waveform; < 0: np.zeros of a negative size):
+ * AMR_E_INVALID with numpy's message.  n_bytes counts characters. */
+#define AMR_TX_HELL 3
 /* natural waveform length of an n_bytes payload (the reference's len(out)), or < 0 */
 int64_t amr_tx_samples(int mode, int64_t n_bytes, double baud, double sample_rate);
 /* device scratch bytes amr_modulate_device needs for this shape */
@@ -542,6 +555,46 @@ int amr_modulate_device(amr_psk_plan *plan, int mode, double baud, double f0, do
                         const uint8_t *d_data, int64_t data_stride, const int64_t *d_n_bytes, int64_t n,
                         float *d_out, int64_t out_stride, int64_t n_out, int16_t *d_pcm, int64_t pcm_stride,
                         void *d_work, int64_t work_bytes);
+
+/* ---- Hellschreiber receiver (hellschreiber.py:155-187) ----------------------
+ * x [n_streams][x_stride] elements of type `elem`, n_samples used per stream.
+ * sps = int(round(sample_rate / baud)); pixel p of a stream is 1 iff
+ * np.mean(x[p*sps:(p+1)*sps] ** 2) > 0.1, evaluated as numpy evaluates it for
+ * that dtype (its pairwise summation order, squares in the array's dtype --
+ * integers wrap --, float16 / float32 summed in float32, everything else in
+ * float64, np.mean's result dtype and numpy's weak-scalar comparison); every
+ * full group of 7 pixels gives one output byte (the first glyph with a row
+ * equal to the 7-bit value, else '?').  out [n_streams][out_stride] bytes,
+ * out_len[n_streams] = pixels / 7.  energy (optional, may be NULL):
+ * [n_streams][pixels] float64, each pixel's np.mean value widened exactly.
+ * sps == 0 is the reference's ValueError: AMR_E_INVALID with range()'s message
+ * in amr_last_error(); a negative sps decodes nothing, as the reference. */
+#define AMR_HELL_ELEM_F32 0
+#define AMR_HELL_ELEM_F64 1
+#define AMR_HELL_ELEM_F16 2
+#define AMR_HELL_ELEM_I8 3         /* raw integers: their values (the square wraps in the dtype) */
+#define AMR_HELL_ELEM_I16 4
+#define AMR_HELL_ELEM_I32 5
+#define AMR_HELL_ELEM_I64 6
+#define AMR_HELL_ELEM_U8 7
+#define AMR_HELL_ELEM_U16 8
+#define AMR_HELL_ELEM_U32 9
+#define AMR_HELL_ELEM_U64 10
+#define AMR_HELL_ELEM_PCM16 11     /* int16 PCM read as int16 / 32768.0 in float64 (AMR_DTYPE_I16's meaning) */
+/* pixels a capture of n_samples holds (n_samples / sps), or < 0 */
+int64_t amr_hell_pixels(int64_t n_samples, double baud, double sample_rate);
+/* device scratch bytes amr_hell_demod_device needs (the pixel's summation tree + the lookup) */
+int64_t amr_hell_work_bytes(double baud, double sample_rate);
+int amr_hell_demod_host(const void *x, int elem, int64_t n_streams, int64_t x_stride, int64_t n_samples, double baud,
+                        double sample_rate, uint8_t *out, int64_t out_stride, int64_t *out_len, double *energy);
+/* device pointers, enqueued on the plan's stream (plan may be NULL: the null stream) */
+int amr_hell_demod_device(amr_psk_plan *plan, const void *d_x, int elem, int64_t n_streams, int64_t x_stride,
+                          int64_t n_samples, double baud, double sample_rate, uint8_t *d_out, int64_t out_stride,
+                          int64_t *d_out_len, double *d_energy, void *d_work, int64_t work_bytes);
+/* the glyph bitmaps the library carries: rows [95][7] (' '..'~'; byte r = pixel
+ * row r, bit i = its i-th pixel on the air) and the receiver's lookup [128];
+ * either may be NULL.  Host only.  Returns the glyph count (95). */
+int amr_hell_glyph_rows(uint8_t *rows, uint8_t *rx_lookup);
 
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
