@@ -64,6 +64,8 @@ EXPORTS = [
     "amr_psk_split_bounds_host", "amr_psk_plan_set_split_strict", "amr_psk_plan_split_strict",
     "amr_psk_plan_last_strict", "amr_psk_split_strict_design",
     "amr_hell_pixels", "amr_hell_work_bytes", "amr_hell_demod_host", "amr_hell_demod_device", "amr_hell_glyph_rows",
+    "amr_conv_encoded_len", "amr_conv_encode_host", "amr_viterbi_work_bytes", "amr_viterbi_decode_device",
+    "amr_viterbi_decode_host",
 ]
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL = 0, 1, 2, 3
@@ -370,6 +372,11 @@ def lib():
             "amr_hell_demod_host": (I32, [P, I32, I64, I64, I64, D, D, P, I64, P, P]),
             "amr_hell_demod_device": (I32, [P, P, I32, I64, I64, I64, D, D, P, I64, P, P, P, I64]),
             "amr_hell_glyph_rows": (I32, [P, P]),
+            "amr_conv_encoded_len": (I64, [I64]),
+            "amr_conv_encode_host": (I32, [P, I64, P, I64, P, I64, P]),
+            "amr_viterbi_work_bytes": (I64, [I64, I64]),
+            "amr_viterbi_decode_device": (I32, [P, P, I64, P, I64, P, I64, P, P, P, I64]),
+            "amr_viterbi_decode_host": (I32, [P, I64, P, I64, P, I64, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -816,6 +823,60 @@ def fec_decode_host(datas):
     check(lib().amr_set_device(default_device()))
     check(lib().amr_fec_decode_host(ptr(buf), stride, ptr(ln), n, ptr(out), stride, ptr(out_len), ptr(ok)))
     return [out[i, :out_len[i]].tobytes() for i in range(n)], [bool(v) for v in ok]
+
+
+VITERBI_MAX_LEN = 1 << 24
+
+
+def is_codeword_len(n: int) -> bool:
+    """A byte length the rate-1/2 K=7 encoder can produce (2 n + 2), up to 2^24."""
+    return n % 2 == 0 and 2 <= n <= VITERBI_MAX_LEN
+
+
+def _pad_rows(datas):
+    n = len(datas)
+    ln = np.array([len(d) for d in datas], np.int64)
+    stride = max(1, int(ln.max()))
+    buf = np.zeros((n, stride), np.uint8)
+    for i, d in enumerate(datas):
+        buf[i, :len(d)] = np.frombuffer(d, np.uint8)
+    return buf, ln, stride
+
+
+def conv_encode(datas):
+    """Batched fec.ConvolutionalEncoder.encode on the GPU (amr_conv_encode_host): list[bytes]."""
+    require_gpu()
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    if n == 0:
+        return []
+    buf, ln, stride = _pad_rows(datas)
+    cap = 2 * int(ln.max()) + 2
+    out = np.zeros((n, cap), np.uint8)
+    out_len = np.zeros(n, np.int64)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_conv_encode_host(ptr(buf), stride, ptr(ln), n, ptr(out), cap, ptr(out_len)))
+    return [out[i, :out_len[i]].tobytes() for i in range(n)]
+
+
+def viterbi_decode(datas):
+    """Batched maximum-likelihood decode of the K=7 code on the GPU
+    (amr_viterbi_decode_host).  Returns (list[bytes], list[int]): the messages
+    and, per codeword, the coded-bit positions in which it differs from the
+    codeword of its decoded message."""
+    require_gpu()
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    if n == 0:
+        return [], []
+    buf, ln, stride = _pad_rows(datas)
+    cap = max(1, stride // 2)
+    out = np.zeros((n, cap), np.uint8)
+    out_len = np.zeros(n, np.int64)
+    metric = np.zeros(n, np.int32)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_viterbi_decode_host(ptr(buf), stride, ptr(ln), n, ptr(out), cap, ptr(out_len), ptr(metric)))
+    return [out[i, :out_len[i]].tobytes() for i in range(n)], [int(v) for v in metric]
 
 
 def fft(x: np.ndarray, inverse: bool = False) -> np.ndarray:

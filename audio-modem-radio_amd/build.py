@@ -19,11 +19,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libamr.so")
+LIB_ID = LIB + ".id"                      # source_hash() of the tree LIB was linked from
 SOURCES = ["psk_kernels.hip", "psk_lane_kernels.hip", "psk_split_kernels.hip", "util_kernels.hip", "fft_kernels.hip", "fsk_kernels.hip", "fsk_exact_kernels.hip", "pocketfft_kernels.hip", "frame_kernels.hip", "tx_kernels.hip",
-           "hell_kernels.hip", "api.cpp", "tx_api.cpp", "hell_api.cpp",
+           "hell_kernels.hip", "viterbi_kernels.hip", "api.cpp", "tx_api.cpp", "hell_api.cpp", "viterbi_api.cpp",
            "fsk_api.cpp", "pocketfft_plan.cpp"]
 HEADERS = ["amr_internal.h", "psk_common.h", "fft.h", "api_common.h", "fsk_exact.h", "pocketfft.h", "pocketfft_dev.h",
-           "iir_design.h", "split_chain.h", "odd_ext.h", "split_strict.h", "hell.h", "hell_glyphs.h", os.path.join(INCLUDE, "amr.h")]
+           "iir_design.h", "split_chain.h", "odd_ext.h", "split_strict.h", "hell.h", "hell_glyphs.h", "viterbi.h", os.path.join(INCLUDE, "amr.h")]
 ARCH = os.environ.get("AMR_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
@@ -57,10 +58,16 @@ def source_hash() -> str:
 def build(force: bool = False, verbose: bool = False) -> str:
     """Rebuild what changed BY CONTENT (each object records the digest of its
     source + headers + flags next to it), never by modification time alone."""
+    bid = source_hash()
+    # a library linked from exactly these sources (its id is written beside it after
+    # the link) needs nothing, also where the objects did not travel with it
+    if not force and os.path.exists(LIB) and os.path.exists(LIB_ID):
+        with open(LIB_ID) as f:
+            if f.read().strip() == bid:
+                return LIB
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hdrs = _headers()
-    bid = source_hash()
     objs = []
     jobs = []
     relink = force or not os.path.exists(LIB)
@@ -94,7 +101,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
                "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
         if verbose:
             print(" ".join(cmd))
+        if os.path.exists(LIB_ID):
+            os.remove(LIB_ID)
         subprocess.run(cmd, check=True)
+    if relink or not os.path.exists(LIB_ID):
+        with open(LIB_ID, "w") as f:
+            f.write(bid + "\n")
     return LIB
 
 

@@ -5,8 +5,15 @@
   ReedSolomonFEC.decode_batch           batched form (one wave per stream)
 Despite its name the reference "Reed-Solomon" is parity-XOR triples plus a
 CRC32 trailer; that is what is reproduced, bit for bit.
-ConvolutionalEncoder / ViterbiDecoder (fec.py:72-155) are kept as plain
-host code for import compatibility; they are outside the hot path.
+ConvolutionalEncoder.encode (fec.py:79-111) and ViterbiDecoder.decode
+(fec.py:126-155) stay host code, byte for byte the reference's -- and the
+latter is the reference's stub, which does not invert the encoder.  Beside
+them, with no reference counterpart:
+  ConvolutionalEncoder.encode_batch     -> k_conv_encode (viterbi_kernels.hip)
+  ViterbiDecoder.decode_ml / decode_ml_batch
+                                        -> k_viterbi: maximum-likelihood
+                                           hard-decision decoding of that code,
+                                           one wavefront per codeword
 """
 from __future__ import annotations
 
@@ -79,9 +86,15 @@ class ConvolutionalEncoder:
             out.append(v)
         return bytes(out)
 
+    def encode_batch(self, datas):
+        """encode() of every element, in one launch on the GPU: list[bytes]."""
+        return _amr.conv_encode(datas)
+
 
 class ViterbiDecoder:
-    """fec.py:114-155 -- the reference's stub (it does not invert the encoder)."""
+    """fec.py:114-155 -- decode() is the reference's stub (it does not invert
+    the encoder); decode_ml / decode_ml_batch are the real decoder, on the GPU.
+    constraint_length is ignored, as in the reference: the polynomials fix K=7."""
 
     def __init__(self, constraint_length=7):
         self.constraint_length = constraint_length
@@ -90,6 +103,8 @@ class ViterbiDecoder:
         self.trellis = {}
 
     def decode(self, data: bytes) -> bytes:
+        """The reference's stub, kept for parity: it drops 12 bits and keeps every
+        second one.  To invert ConvolutionalEncoder.encode use decode_ml."""
         bits = [(byte >> (7 - i)) & 1 for byte in data for i in range(8)]
         if len(bits) >= 12:
             bits = bits[:-12]
@@ -102,3 +117,21 @@ class ViterbiDecoder:
                     v = (v << 1) | used[i + j]
             out.append(v)
         return bytes(out)
+
+    def decode_ml(self, data: bytes) -> bytes:
+        """The message whose codeword is nearest (Hamming) to `data`, a hard-decision
+        codeword of ConvolutionalEncoder.encode: 2 n + 2 bytes give n.  ValueError
+        for a length the encoder cannot produce."""
+        return self.decode_ml_batch([data])[0]
+
+    def decode_ml_batch(self, datas, return_errors: bool = False):
+        """decode_ml of every element in one launch: list[bytes]; with
+        return_errors=True also list[int], the coded bits each input differs in
+        from the codeword of its decoded message."""
+        datas = [bytes(d) for d in datas]
+        for i, d in enumerate(datas):
+            if not _amr.is_codeword_len(len(d)):
+                raise ValueError(f"codeword {i}: {len(d)} bytes is not a length of this code "
+                                 f"(even, 2 .. {_amr.VITERBI_MAX_LEN})")
+        outs, errs = _amr.viterbi_decode(datas)
+        return (outs, errs) if return_errors else outs

@@ -42,6 +42,10 @@
  *   amr_hell_demod_host     hellschreiber.hellschreiber_demodulate
  *                           (hellschreiber.py:155-187), batched; AMR_TX_HELL is
  *                           hellschreiber_modulate (hellschreiber.py:109-152)
+ *   amr_conv_encode_host    fec.ConvolutionalEncoder.encode  fec.py:79-111, batched
+ *   amr_viterbi_decode_host the maximum-likelihood decoder of that code, batched
+ *                           (no reference counterpart: fec.ViterbiDecoder.decode,
+ *                           fec.py:126-155, is a stub and stays one in fec.py)
  *   amr_allgather           the gather of decoded bytes across GPUs (RCCL)
  *
  * Status: every function returns AMR_OK (0) or a negative AMR_E_* code;
@@ -79,7 +83,9 @@ extern "C" {
                                   split's strict mode (amr_fsk_plan_set_split_strict ...)
                                   additions under 5 (nothing existing changed): the Hellschreiber
                                   receiver (amr_hell_pixels, amr_hell_work_bytes, amr_hell_demod_host /
-                                  _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL */
+                                  _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL; the
+                                  convolutional code (amr_conv_encoded_len, amr_conv_encode_host,
+                                  amr_viterbi_work_bytes, amr_viterbi_decode_host / _device) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -595,6 +601,40 @@ int amr_hell_demod_device(amr_psk_plan *plan, const void *d_x, int elem, int64_t
  * row r, bit i = its i-th pixel on the air) and the receiver's lookup [128];
  * either may be NULL.  Host only.  Returns the glyph count (95). */
 int amr_hell_glyph_rows(uint8_t *rows, uint8_t *rx_lookup);
+
+/* ---- convolutional code (fec.py:72-111) and its Viterbi decoder ---------------
+ * Rate 1/2, K = 7, polynomials 171 / 133 octal, register ((sr << 1) | bit) & 0x7F,
+ * message bits MSB-first then 6 zero flush bits, the coded bits packed MSB-first;
+ * a message of n bytes is a codeword of 2 n + 2 bytes whose last byte holds the
+ * final 4 bits in its LOW nibble (the reference's packing).  The encoder is
+ * fec.ConvolutionalEncoder.encode for a batch.  The decoder is a
+ * maximum-likelihood hard-decision Viterbi decoder over the whole codeword
+ * (Hamming branch metrics, int32 path metrics, start and end in state 0, a tie
+ * keeps the predecessor with the older bit clear); the reference has none -- its
+ * ViterbiDecoder.decode is a stub.  A length L is a codeword length when it is
+ * even and 2 <= L <= 2^24.  in [n][in_stride] bytes, in_len[n]; out
+ * [n][out_stride] bytes, out_len[n]; metric[n] = the number of coded-bit
+ * positions in which the input differs from the codeword of the decoded message
+ * (the last byte's high nibble is not looked at).  Only out_len[i] bytes of an
+ * output row are written. */
+/* 2 n_bytes + 2, or < 0 for n_bytes < 0 */
+int64_t amr_conv_encoded_len(int64_t n_bytes);
+/* in_len[i] <= in_stride message bytes per row; out_stride >= 2 * longest + 2 */
+int amr_conv_encode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, int64_t n, uint8_t *out,
+                         int64_t out_stride, int64_t *out_len);
+/* device scratch bytes amr_viterbi_decode_device needs for n rows of in_stride bytes: 512 bytes of
+ * survivor decisions per 64 trellis steps of the longest codeword a row can hold.  Host arithmetic. */
+int64_t amr_viterbi_work_bytes(int64_t in_stride, int64_t n);
+/* device pointers, enqueued on the plan's stream (plan may be NULL: the null stream).  The lengths are
+ * read on the device: a row whose length is not a codeword length, or exceeds in_stride, gets
+ * out_len 0 and metric -1 and nothing else of it is touched.  out_stride >= in_stride / 2 - 1. */
+int amr_viterbi_decode_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_stride, const int64_t *d_in_len,
+                              int64_t n, uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int32_t *d_metric,
+                              void *d_work, int64_t work_bytes);
+/* host pointers; a length that is not a codeword length is AMR_E_INVALID (the message names the row)
+ * before any device work; large batches are decoded in chunks of bounded scratch */
+int amr_viterbi_decode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, int64_t n, uint8_t *out,
+                            int64_t out_stride, int64_t *out_len, int32_t *metric);
 
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
