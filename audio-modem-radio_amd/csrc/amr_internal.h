@@ -81,8 +81,45 @@ struct PskBuffers {
   const double* edge;
 };
 
-// the time-split strict bound's block of outputs (split_strict.h, psk_split_kernels.hip KB)
+// the time-split strict bound's block of outputs (split_strict.h, split_bound.h KB1 / KB2)
 constexpr int kStrictBlk = 16;
+// the step bound's u2 = 2 U, U = u (1 + u)^4 rounded up (split_strict.h)
+constexpr double kStrictU2 = 2.0 * 0x1p-53 * (1.0 + 0x1p-50);
+
+// One filter's strict band-pass design as the kernels read it (split_strict.h
+// strict_design_bp / strict_bp_view; the PSK split holds one, the FSK split
+// one per tone): the convolution-start bound tables, the block kernels and
+// their cut remainders, and the per-step / per-pass constants
+struct StrictBp {
+  const double* kabs;         // [w] sum_i |K_i[m]|
+  const double* z0abs;        // [w + 1] sum_i |Z0_i[t]|
+  const double *W, *K12, *HS, *GS, *TZ;
+  int nw, nk, nh, nz, k12_off;
+  double w_tail, k12_tail, hs_tail, tz_tail;
+  double gam;                 // KS0 / FS0's dot-product rounding factor (gamma_n + the tables' 2u)
+  double kx, ky;              // the step bound's constants
+  double g1x, gmax;           // 1 + sum_m max_j |g_j(m)|, its max
+  double hz, tk, zi_sum, zb;  // ||h||_1 + max|tz|; truncation per unit peak; sum|zi|; state sum per unit peak
+};
+
+// The strict bound's scratch rows, one per filter run (PSK: per stream; FSK:
+// per (stream, tone)), sstride doubles apart: D1 blocks [nb1] | D2 blocks
+// [nb1] | chunk start bounds pass 1 [c] | pass 2 [c] | E1 blocks [nb1] | S1
+// blocks [nb1] | E2 blocks [nb1] | the modem's own regions (strict_off_end)
+struct StrictRows {
+  double* sc;
+  int64_t sstride;
+  int64_t nb1;                // blocks per pass: ceil(m1 / kStrictBlk)
+  int64_t c;                  // chunks per pass
+};
+__host__ __device__ inline int64_t strict_off_d1(const StrictRows&) { return 0; }
+__host__ __device__ inline int64_t strict_off_d2(const StrictRows& r) { return r.nb1; }
+__host__ __device__ inline int64_t strict_off_ds1(const StrictRows& r) { return 2 * r.nb1; }
+__host__ __device__ inline int64_t strict_off_ds2(const StrictRows& r) { return 2 * r.nb1 + r.c; }
+__host__ __device__ inline int64_t strict_off_e1(const StrictRows& r) { return 2 * r.nb1 + 2 * r.c; }
+__host__ __device__ inline int64_t strict_off_s1(const StrictRows& r) { return 3 * r.nb1 + 2 * r.c; }
+__host__ __device__ inline int64_t strict_off_e2(const StrictRows& r) { return 4 * r.nb1 + 2 * r.c; }
+__host__ __device__ inline int64_t strict_off_end(const StrictRows& r) { return 5 * r.nb1 + 2 * r.c; }
 
 // PSK time-split layout (psk_split_kernels.hip): each filtfilt
 // pass cut into chunks of L outputs, one lane per chunk, each started w
@@ -113,37 +150,20 @@ struct PskSplit {
   // and their maxima per stream to bnd; KS5 turns them into a bound per symbol
   int strict;
   unsigned long long* bnd;   // [B][8] bits (cleared per launch): D1max, -, max|y1|, D2max, -, max|f|
-  const double* kabs;        // [w1] sum_i |K_i[m]|
-  const double* z0abs;       // [w1 + 1] sum_i |Z0_i[t]|
+  StrictBp sb;               // the band-pass design (device tables + constants)
   const double* lpc;         // [n_sym] the band-pass error's reach to symbol k (the low-pass stage)
-  double gam;                // KS0's dot-product rounding factor (gamma_n + the tables' 2u)
-  double u2, kx, ky;         // the step bound's constants
-  double g1x, gmax;          // 1 + sum_m max_j |g_j(m)|, its max
-  double hz, tk, zi_sum, zb; // ||h||_1 + max|tz|; truncation per unit peak; sum|zi|; state sum per unit peak
   double c3;                 // the low-pass's own rounding, truncation, extension rounding per unit P3
-  // the block bound (KB; split_strict.h kStrictBlk): kernels and their cut remainders
-  const double *kW, *kK12, *kHS, *kGS, *kTZ;
-  int nw, nk, k12_off, nh, nz;
-  double w_tail, k12_tail, hs_tail, tz_tail, lp_tail;
+  double lp_tail;            // the low-pass window's cut remainder (x max X)
   int64_t lp_rad;
-  // per-stream scratch (stride sstride doubles): D1 blocks [nb1] | D2 blocks [nb1] | chunk start bounds
-  // pass 1 [c1] | pass 2 [c1] | E1 blocks [nb1] | S1 blocks [nb1] | E2 blocks [nb1] | X blocks [nbs] |
-  // e(k) [n_sym] | scalars [4]: E1max, Fmax, Xmax, P3 (negative: the caps failed, the stream is flagged)
-  double* sc;
-  int64_t sstride, nb1, nbs;
+  // per-stream scratch: the common regions, then X blocks [nbs] | e(k) [n_sym] | scalars [4]:
+  // E1max, Fmax, Xmax, P3 (negative: the caps failed, the stream is flagged)
+  StrictRows rows;
+  int64_t nbs;
   double* ebound;            // diagnostic (amr_psk_split_bounds_host): copy e(k) and the scalars out
 };
-
-// offsets into PskSplit::sc
-__host__ __device__ inline int64_t strict_off_d1(const PskSplit&) { return 0; }
-__host__ __device__ inline int64_t strict_off_d2(const PskSplit& s) { return s.nb1; }
-__host__ __device__ inline int64_t strict_off_ds1(const PskSplit& s) { return 2 * s.nb1; }
-__host__ __device__ inline int64_t strict_off_ds2(const PskSplit& s) { return 2 * s.nb1 + s.c1; }
-__host__ __device__ inline int64_t strict_off_e1(const PskSplit& s) { return 2 * s.nb1 + 2 * s.c1; }
-__host__ __device__ inline int64_t strict_off_s1(const PskSplit& s) { return 3 * s.nb1 + 2 * s.c1; }
-__host__ __device__ inline int64_t strict_off_e2(const PskSplit& s) { return 4 * s.nb1 + 2 * s.c1; }
-__host__ __device__ inline int64_t strict_off_x(const PskSplit& s) { return 5 * s.nb1 + 2 * s.c1; }
-__host__ __device__ inline int64_t strict_off_e(const PskSplit& s) { return 5 * s.nb1 + 2 * s.c1 + s.nbs; }
+// PskSplit's own regions of a scratch row
+__host__ __device__ inline int64_t strict_off_x(const PskSplit& s) { return strict_off_end(s.rows); }
+__host__ __device__ inline int64_t strict_off_e(const PskSplit& s) { return strict_off_end(s.rows) + s.nbs; }
 
 // FSK live-column layout.  A four-step length n = n1 * n2
 // (sample i = j1 + n1 * j2) with n1 % sps == 0: every decision window of
@@ -239,19 +259,6 @@ __host__ __device__ inline double amb_scale(double peak, double tau = kAmbTau) {
   return 8.0 * d * d;
 }
 
-// One filter's strict band-pass design as the kernels read it (split_strict.h
-// strict_design_bp; the FSK split's strict mode holds one per tone): the
-// convolution-start bound tables, the block kernels and their cut remainders,
-// and the per-step / per-pass constants
-struct StrictBp {
-  const double* kabs;         // [w]
-  const double* z0abs;        // [w + 1]
-  const double *W, *K12, *HS, *GS, *TZ;
-  int nw, nk, nh, nz, k12_off;
-  double w_tail, k12_tail, hs_tail, tz_tail;
-  double gam, kx, ky, g1x, gmax, hz, tk, zi_sum, zb;
-};
-
 // FSK time-split F1 (fsk_kernels.hip FS1-FS3):
 // each filtfilt pass of both tones cut into chunks of L outputs, one lane per
 // (chunk, tone), every chunk started w samples early from a zero state.  Its
@@ -266,28 +273,20 @@ struct FskSplit {
   double tau;                 // kAmbTau + tau_env: F2's margin scale for these streams
   double* y1;                 // [B][2][m1] forward outputs (tone-major per stream)
   unsigned long long* peak;   // [B] bits of max |ext x| (cleared per launch)
-  // chunk start states by convolution (FS0, as the PSK split's KS0): conv = 1 uses them
+  // chunk start states by convolution (FS0): conv = 1 uses them
   int conv;
   const double* ktab;         // [2 tones][w][6] (iir_design.h split_state_tables)
   const double* z0tab;        // [2 tones][w + 1][6]
   double* zs;                 // [B][2][c][6] start states, FS0 -> FS1 (then reused for FS2)
   // STRICT (round 6; split_strict.h strict_design_bp per tone, fsk_kernels.hip
-  // FS0-FS2 with ST, KF1-KF2, FS3): F2's margin from a bound on |z_split -
-  // z_serial| that holds for every input, in place of kappa * peak
+  // FS0-FS2 with ST, KF1-KF2 (split_bound.h), FS3): F2's margin from a bound on
+  // |z_split - z_serial| that holds for every input, in place of kappa * peak
   int strict;
   StrictBp sb[2];             // the per-tone design (device tables + constants)
-  double u2;
   double hl1;                 // ||ifft(h)||_1 of scipy.signal.hilbert's kernel at n
   unsigned long long* bnd;    // [B][2][8] bits: D1max, E1max, max|y1|, D2max, S1max, -, Fmax, -
-  double* sc;                 // [B][2][sstride]: d1 nb1 | d2 nb1 | ds1 c | ds2 c | e1 nb1 | s1 nb1 | e2 nb1
-  int64_t sstride, nb1;
+  StrictRows rows;            // [B][2] rows, the common regions alone
 };
-__host__ __device__ inline int64_t fsk_strict_off_d2(const FskSplit& s) { return s.nb1; }
-__host__ __device__ inline int64_t fsk_strict_off_ds1(const FskSplit& s) { return 2 * s.nb1; }
-__host__ __device__ inline int64_t fsk_strict_off_ds2(const FskSplit& s) { return 2 * s.nb1 + s.c; }
-__host__ __device__ inline int64_t fsk_strict_off_e1(const FskSplit& s) { return 2 * s.nb1 + 2 * s.c; }
-__host__ __device__ inline int64_t fsk_strict_off_s1(const FskSplit& s) { return 3 * s.nb1 + 2 * s.c; }
-__host__ __device__ inline int64_t fsk_strict_off_e2(const FskSplit& s) { return 4 * s.nb1 + 2 * s.c; }
 
 struct FskIir {            // [tone][tap], tone 0 = mark
   double b[2][8];

@@ -269,10 +269,11 @@ struct amr_psk_plan {
   int64_t split_zs_bytes = 0;
   // the split layout's STRICT bound (split_strict.h): -1 = the process default
   // (AMR_PSK_SPLIT_STRICT=1), else amr_psk_plan_set_split_strict; designed on
-  // the first strict call (the device tables kabs | z0abs | lpc in strict_tab,
-  // the per-stream maxima in strict_bnd)
+  // the first strict call (the device tables, split_strict.h strict_bp_append |
+  // lpc, in strict_tab, the per-stream maxima in strict_bnd; strict_ok once
+  // both are on the device)
   int strict_mode = -1;
-  bool strict_designed = false;
+  bool strict_designed = false, strict_ok = false;
   StrictDesign sdes;
   double* strict_tab = nullptr;
   unsigned long long* strict_bnd = nullptr;
@@ -815,7 +816,7 @@ int amr_psk_split_strict_design(const double* bp_b, const double* bp_a, const do
   split_state_tables(bp, w1, tab.data(), tab.data() + (size_t)w1 * 8);
   const StrictDesign d = strict_design(bp, lp, tab.data(), tab.data() + (size_t)w1 * 8, w1, w2, n, first, sps, n_sym);
   // the device table's layout: kabs | z0abs | lpc | W | K12 | HS | GS | TZ
-  const double v[32] = {d.g1x, d.gmax, d.hz, d.tk, d.zi_sum, d.zb, d.kx, d.ky, 2.0 * 0x1p-53 * (1.0 + 0x1p-50),
+  const double v[32] = {d.g1x, d.gmax, d.hz, d.tk, d.zi_sum, d.zb, d.kx, d.ky, kStrictU2,
                         d.gam, d.c3, (double)w1, (double)w2, (double)n_sym, (double)d.W.size(), (double)d.K12.size(),
                         (double)d.HS.size(), (double)d.GS.size(), (double)d.TZ.size(), (double)d.k12_off, d.w_tail,
                         d.k12_tail, d.hs_tail, d.tz_tail, d.lp_tail, (double)d.lp_rad, d.ok ? 1.0 : 0.0, kappa};
@@ -976,7 +977,7 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
   sp.z0tab = pl->split_tab ? pl->split_tab + (size_t)sp.w1 * 8 : nullptr;
   sp.zs = pl->split_zs;
   pl->split_L = sp.L;
-  if (pl->strict_designed && pl->sdes.ok && split_strict_on(pl) && sp.conv) {
+  if (pl->strict_ok && split_strict_on(pl) && sp.conv) {
     const StrictDesign& d = pl->sdes;
     // chunks on block boundaries (the per-block step bounds stay within a lane)
     sp.L = (sp.L + kStrictBlk - 1) / kStrictBlk * kStrictBlk;
@@ -985,48 +986,22 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
     pl->split_L = sp.L;
     sp.strict = 1;
     sp.bnd = pl->strict_bnd;
-    const double* t = pl->strict_tab;
-    sp.kabs = t;
-    sp.z0abs = t + sp.w1;
-    sp.lpc = t + 2 * sp.w1 + 1;
-    const double* k = sp.lpc + pl->p.n_sym;
-    sp.kW = k;
-    sp.kK12 = sp.kW + d.W.size();
-    sp.kHS = sp.kK12 + d.K12.size();
-    sp.kGS = sp.kHS + d.HS.size();
-    sp.kTZ = sp.kGS + d.GS.size();
-    sp.nw = (int)d.W.size();
-    sp.nk = (int)d.K12.size();
-    sp.k12_off = d.k12_off;
-    sp.nh = (int)d.HS.size();
-    sp.nz = (int)d.TZ.size();
-    sp.w_tail = d.w_tail;
-    sp.k12_tail = d.k12_tail;
-    sp.hs_tail = d.hs_tail;
-    sp.tz_tail = d.tz_tail;
+    sp.sb = strict_bp_view(d, pl->strict_tab);
+    sp.lpc = pl->strict_tab + strict_bp_doubles(d);
+    sp.c3 = d.c3;
     sp.lp_tail = d.lp_tail;
     sp.lp_rad = d.lp_rad;
-    sp.gam = d.gam;
-    sp.u2 = 2.0 * 0x1p-53 * (1.0 + 0x1p-50);
-    sp.kx = d.kx;
-    sp.ky = d.ky;
-    sp.g1x = d.g1x;
-    sp.gmax = d.gmax;
-    sp.hz = d.hz;
-    sp.tk = d.tk;
-    sp.zi_sum = d.zi_sum;
-    sp.zb = d.zb;
-    sp.c3 = d.c3;
-    sp.nb1 = (pl->p.m1 + kStrictBlk - 1) / kStrictBlk;
+    sp.rows.nb1 = (pl->p.m1 + kStrictBlk - 1) / kStrictBlk;
+    sp.rows.c = sp.c1;
     sp.nbs = (pl->p.n + kStrictBlk - 1) / kStrictBlk;
-    sp.sstride = 5 * sp.nb1 + 2 * sp.c1 + sp.nbs + pl->p.n_sym + 4;
+    sp.rows.sstride = strict_off_e(sp) + pl->p.n_sym + 4;
   }
   return sp;
 }
 // the strict scratch for B streams of this call's geometry
 int ensure_strict_sc(amr_psk_plan* pl, PskSplit& sp, int64_t B) {
   if (!sp.strict) return AMR_OK;
-  const int64_t need = B * sp.sstride * 8;
+  const int64_t need = B * sp.rows.sstride * 8;
   if (pl->strict_sc_bytes < need || !pl->strict_sc) {
     HIP_TRY(hipStreamSynchronize(pl->stream));
     if (pl->strict_sc) HIP_TRY(hipFree(pl->strict_sc));
@@ -1035,7 +1010,7 @@ int ensure_strict_sc(amr_psk_plan* pl, PskSplit& sp, int64_t B) {
     HIP_TRY(hipMalloc((void**)&pl->strict_sc, (size_t)need));
     pl->strict_sc_bytes = need;
   }
-  sp.sc = pl->strict_sc;
+  sp.rows.sc = pl->strict_sc;
   return AMR_OK;
 }
 // the strict mode's design and device tables, on the first strict call
@@ -1049,13 +1024,13 @@ int strict_prepare(amr_psk_plan* pl) {
   pl->sdes = strict_design(pl->bp, pl->lp, tab.data(), tab.data() + (size_t)w * 8, w, pl->split_w2, pl->p.n,
                            pl->p.first, pl->p.sps, pl->p.n_sym);
   if (!pl->sdes.ok) return AMR_OK;
-  std::vector<double> dev(pl->sdes.kabs);
-  for (const std::vector<double>* v : {&pl->sdes.z0abs, &pl->sdes.lpc, &pl->sdes.W, &pl->sdes.K12, &pl->sdes.HS,
-                                       &pl->sdes.GS, &pl->sdes.TZ})
-    dev.insert(dev.end(), v->begin(), v->end());
+  std::vector<double> dev;
+  strict_bp_append(pl->sdes, dev);
+  dev.insert(dev.end(), pl->sdes.lpc.begin(), pl->sdes.lpc.end());
   HIP_TRY(hipMalloc((void**)&pl->strict_tab, dev.size() * 8));
   HIP_TRY(hipMemcpy(pl->strict_tab, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc((void**)&pl->strict_bnd, (size_t)pl->max_streams * 64));
+  pl->strict_ok = true;
   return AMR_OK;
 }
 // The lane layout's float32 hand-off: the band-pass output f
@@ -1348,7 +1323,7 @@ int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B,
     HIP_TRY(launch_psk_split_slice(b, pl->p, sp, pl->stream));
     // e(k) and the scalars of every stream, packed [B][S + 4]
     const int64_t S = pl->p.n_sym;
-    HIP_TRY(hipMemcpy2DAsync(ebound, (size_t)(S + 4) * 8, sp.sc + strict_off_e(sp), (size_t)sp.sstride * 8,
+    HIP_TRY(hipMemcpy2DAsync(ebound, (size_t)(S + 4) * 8, sp.rows.sc + strict_off_e(sp), (size_t)sp.rows.sstride * 8,
                              (size_t)(S + 4) * 8, (size_t)B, hipMemcpyDeviceToDevice, pl->stream));
   }
   return AMR_OK;

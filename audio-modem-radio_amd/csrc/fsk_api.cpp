@@ -531,7 +531,7 @@ FskSplit fsk_split_params(amr_fsk_plan* pl, int64_t B, int64_t L) {
 }
 
 // STRICT: the per-tone designs from FS0's tables (host arithmetic, once) and
-// their device copy: per tone kabs [w] | z0abs [w + 1] | W | K12 | HS | GS | TZ
+// their device copy: per tone split_strict.h strict_bp_append's tables
 int fsk_strict_prepare(amr_fsk_plan* pl) {
   if (pl->strict_designed) return AMR_OK;
   pl->strict_designed = true;
@@ -554,10 +554,7 @@ int fsk_strict_prepare(amr_fsk_plan* pl) {
   }
   if (!ok) return AMR_OK;
   std::vector<double> tab;
-  for (int t = 0; t < 2; ++t)
-    for (const std::vector<double>* v : {&pl->sdes[t].kabs, &pl->sdes[t].z0abs, &pl->sdes[t].W, &pl->sdes[t].K12,
-                                         &pl->sdes[t].HS, &pl->sdes[t].GS, &pl->sdes[t].TZ})
-      tab.insert(tab.end(), v->begin(), v->end());
+  for (int t = 0; t < 2; ++t) strict_bp_append(pl->sdes[t], tab);
   HIP_TRY(hipMalloc((void**)&pl->strict_tab, tab.size() * 8));
   HIP_TRY(hipMemcpy(pl->strict_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
   pl->strict_tab_n = (int64_t)tab.size();
@@ -570,9 +567,10 @@ int ensure_fsk_strict(amr_fsk_plan* pl, FskSplit& sp, int64_t B) {
   // (a diagnostic's forced chunk off block boundaries runs without it)
   if (!sp.conv || !fsk_split_strict_on(pl) || !pl->strict_ok || sp.L % kStrictBlk != 0) return AMR_OK;
   const int64_t m1 = pl->p.n + 2 * (int64_t)pl->p.pad;
-  sp.nb1 = (m1 + kStrictBlk - 1) / kStrictBlk;
-  sp.sstride = 5 * sp.nb1 + 2 * sp.c;
-  const int64_t need = B * 2 * sp.sstride * 8;
+  sp.rows.nb1 = (m1 + kStrictBlk - 1) / kStrictBlk;
+  sp.rows.c = sp.c;
+  sp.rows.sstride = strict_off_end(sp.rows);
+  const int64_t need = B * 2 * sp.rows.sstride * 8;
   if (pl->strict_sc_bytes < need || !pl->strict_sc) {
     HIP_TRY(hipStreamSynchronize(pl->stream));
     if (pl->strict_sc) (void)hipFree(pl->strict_sc);
@@ -594,47 +592,11 @@ int ensure_fsk_strict(amr_fsk_plan* pl, FskSplit& sp, int64_t B) {
     pl->strict_bytes += B * 2 * 64;
   }
   sp.strict = 1;
-  sp.u2 = 2.0 * 0x1p-53 * (1.0 + 0x1p-50);
   sp.hl1 = pl->split_hl1;
-  sp.sc = pl->strict_sc;
+  sp.rows.sc = pl->strict_sc;
   sp.bnd = pl->strict_bnd;
-  const double* o = pl->strict_tab;
-  for (int t = 0; t < 2; ++t) {
-    const StrictDesign& d = pl->sdes[t];
-    StrictBp& b = sp.sb[t];
-    b.kabs = o;
-    o += d.kabs.size();
-    b.z0abs = o;
-    o += d.z0abs.size();
-    b.W = o;
-    o += d.W.size();
-    b.K12 = o;
-    o += d.K12.size();
-    b.HS = o;
-    o += d.HS.size();
-    b.GS = o;
-    o += d.GS.size();
-    b.TZ = o;
-    o += d.TZ.size();
-    b.nw = (int)d.W.size();
-    b.nk = (int)d.K12.size();
-    b.nh = (int)d.HS.size();
-    b.nz = (int)d.TZ.size();
-    b.k12_off = d.k12_off;
-    b.w_tail = d.w_tail;
-    b.k12_tail = d.k12_tail;
-    b.hs_tail = d.hs_tail;
-    b.tz_tail = d.tz_tail;
-    b.gam = d.gam;
-    b.kx = d.kx;
-    b.ky = d.ky;
-    b.g1x = d.g1x;
-    b.gmax = d.gmax;
-    b.hz = d.hz;
-    b.tk = d.tk;
-    b.zi_sum = d.zi_sum;
-    b.zb = d.zb;
-  }
+  sp.sb[0] = strict_bp_view(pl->sdes[0], pl->strict_tab);
+  sp.sb[1] = strict_bp_view(pl->sdes[1], pl->strict_tab + strict_bp_doubles(pl->sdes[0]));
   return AMR_OK;
 }
 // the tables and this call's zs in split_cz (grown as needed; counted in
@@ -1527,7 +1489,7 @@ int amr_fsk_split_strict_design(const double* b, const double* a, const double* 
   const bool ok = strict_design_bp(f, tab.data(), tab.data() + (size_t)w * N, w, d, strict_detail::responses(f)) &&
                   d.g1x * (d.kx + 2.0 * d.ky) < 0.125;
   // the PSK entry's layout (amr_psk_split_strict_design) without the low-pass
-  const double v[32] = {d.g1x, d.gmax, d.hz, d.tk, d.zi_sum, d.zb, d.kx, d.ky, 2.0 * 0x1p-53 * (1.0 + 0x1p-50),
+  const double v[32] = {d.g1x, d.gmax, d.hz, d.tk, d.zi_sum, d.zb, d.kx, d.ky, kStrictU2,
                         d.gam, 0.0, (double)w, 0.0, 0.0, (double)d.W.size(), (double)d.K12.size(),
                         (double)d.HS.size(), (double)d.GS.size(), (double)d.TZ.size(), (double)d.k12_off, d.w_tail,
                         d.k12_tail, d.hs_tail, d.tz_tail, 0.0, 0.0, ok ? 1.0 : 0.0, 0.0};

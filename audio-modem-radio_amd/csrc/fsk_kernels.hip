@@ -30,6 +30,7 @@
 
 #include "amr_internal.h"
 #include "odd_ext.h"
+#include "split_bound.h"
 #include "split_chain.h"
 
 namespace amr {
@@ -649,24 +650,21 @@ __device__ __forceinline__ void fsk_split_warm(double (&z)[6], const double (&b)
 }
 
 // FS0 (sp.conv): a chunk's start state by convolution instead of a w-step
-// warm-up (split_chain.h split_conv_state; the PSK split's KS0): one wave
-// per (chunk, tone), four per workgroup, -> zs; before FS1 over ext(x) and
-// again before FS2 over y1 reversed
+// warm-up (split_chain.h split_conv_state): one wave per (chunk, tone), four
+// per workgroup, -> zs; before FS1 over ext(x) and again before FS2 over y1
+// reversed
 // STRICT (FskSplit::strict): the (stream, tone) scratch row and its bounds
 __device__ __forceinline__ double* fsk_strict_row(const FskSplit& sp, int64_t s, int tone) {
-  return sp.sc + ((size_t)s * 2 + tone) * sp.sstride;
+  return sp.rows.sc + ((size_t)s * 2 + tone) * sp.rows.sstride;
 }
 __device__ __forceinline__ ConvBound fsk_conv_bound(const FskSplit& sp, int64_t s, int tone, int64_t off) {
   const StrictBp& d = sp.sb[tone];
   return ConvBound{d.kabs, d.z0abs, d.gam, fsk_strict_row(sp, s, tone) + off};
 }
-// the rounding one step of scipy's order commits, summed over states (split_strict.h):
-// u2 sum_{i>=1} |z_i| + kx |x| + ky |y|, the pre-step |z1..z5| in this pairing
+// the pre-step states' sum_{i>=1} |z_i| of one step (split_bound.h StepBound),
+// z1..z5 in this pairing
 __device__ __forceinline__ double fsk_step_sz(const double (&z)[6]) {
   return ((fabs(z[1]) + fabs(z[2])) + (fabs(z[3]) + fabs(z[4]))) + fabs(z[5]);
-}
-__device__ __forceinline__ unsigned long long fsk_abs_bits(double v) {
-  return (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
 }
 
 template <typename T, bool ST>
@@ -689,7 +687,7 @@ __global__ __launch_bounds__(256) void k_fsk_split_state_fwd(const void* xv, int
         return ox.right(j - pad - n);
       },
       sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6,
-      ST ? fsk_conv_bound(sp, s, tone, fsk_strict_off_ds1(sp) + c) : ConvBound{});
+      ST ? fsk_conv_bound(sp, s, tone, strict_off_ds1(sp.rows) + c) : ConvBound{});
 }
 template <bool ST>
 __global__ __launch_bounds__(256) void k_fsk_split_state_bwd(FskParams p, FskSplit sp) {
@@ -703,7 +701,7 @@ __global__ __launch_bounds__(256) void k_fsk_split_state_bwd(FskParams p, FskSpl
   split_conv_state<6, ST>(
       sp.ktab + (size_t)tone * sp.w * 6, sp.z0tab + (size_t)tone * (sp.w + 1) * 6, sp.w, c * sp.L, y1[m1 - 1],
       [&](int64_t k) { return y1[m1 - 1 - k]; }, sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6,
-      ST ? fsk_conv_bound(sp, s, tone, fsk_strict_off_ds2(sp) + c) : ConvBound{});
+      ST ? fsk_conv_bound(sp, s, tone, strict_off_ds2(sp.rows) + c) : ConvBound{});
 }
 
 // FS1: forward pass over ext(x) (odd extension in the input's precision, as
@@ -726,47 +724,25 @@ __global__ __launch_bounds__(64) void k_fsk_split_fwd(const void* xv, int64_t x_
 #pragma unroll
   for (int i = 0; i < 7; ++i) { b[i] = f.b[tone][i]; a[i] = f.a[tone][i]; }
   const OddExt<T> ox(x, p.edge, s, n, pad);
-  int64_t j = o0 - sp.w;
-  if (sp.conv) {   // FS0's start state
-    j = o0;
-    const double* zs = sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = zs[i];
-  } else if (j <= 0) {
-    j = 0;
-    const double e0 = ox.left(0);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = f.zi[tone][i] * e0;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = 0.0;
-  }
+  int64_t j = split_chunk_start(z, sp.conv ? sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6 : nullptr, f.zi[tone],
+                                [&] { return ox.left(0); }, o0, sp.w);
   double* __restrict__ y1 = sp.y1 + ((size_t)s * 2 + tone) * m1;
   unsigned long long pk = 0;
-  // ST: this chunk's largest step bound and |y1|, and the step bounds summed
-  // per block of kStrictBlk outputs (chunks start on block boundaries)
-  [[maybe_unused]] double dmax = 0.0, ymax = 0.0, dsum = 0.0;
-  [[maybe_unused]] int dcnt = 0;
-  [[maybe_unused]] double* dblk = ST ? fsk_strict_row(sp, s, tone) : nullptr;
-  [[maybe_unused]] const double kx = ST ? sp.sb[tone].kx : 0.0, ky = ST ? sp.sb[tone].ky : 0.0;
+  // ST: this chunk's step bounds (D1 blocks, the largest) and largest |y1|
+  [[maybe_unused]] StepBound acc{ST ? sp.sb[tone].kx : 0.0, ST ? sp.sb[tone].ky : 0.0,
+                                ST ? fsk_strict_row(sp, s, tone) + strict_off_d1(sp.rows) : nullptr};
+  [[maybe_unused]] double ymax = 0.0;
   auto out = [&](int64_t jj, double e) {
     if constexpr (ST) {
       const double sz = fsk_step_sz(z);
       const double y = fsk_step<MODE>(z, b, a, e);
       y1[jj] = y;
-      const double dd = __builtin_fma(sp.u2, sz, __builtin_fma(kx, fabs(e), ky * fabs(y)));
-      dmax = fmax(dmax, dd);
-      dsum += dd;
-      if (++dcnt == kStrictBlk) {
-        dblk[jj / kStrictBlk] = dsum;
-        dsum = 0.0;
-        dcnt = 0;
-      }
+      acc.add(sz, e, y, jj);
       ymax = fmax(ymax, fabs(y));                 // (NaN / inf input: the peak test flags the stream)
     } else {
       y1[jj] = fsk_step<MODE>(z, b, a, e);
     }
-    const unsigned long long bits = fsk_abs_bits(e);
+    const unsigned long long bits = abs_bits(e);
     pk = bits > pk ? bits : pk;
   };
   auto body = [&](int64_t jj, double e) {
@@ -785,9 +761,9 @@ __global__ __launch_bounds__(64) void k_fsk_split_fwd(const void* xv, int64_t x_
   for (; j < o1; ++j) body(j, ox.right(j - pad - n));
   if (tone == 0) atomicMax(&sp.peak[s], pk);
   if constexpr (ST) {
-    if (dcnt > 0) dblk[(o1 - 1) / kStrictBlk] = dsum;   // the pass's last, partial block
-    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 0, fsk_abs_bits(dmax));
-    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 2, fsk_abs_bits(ymax));
+    acc.finish(o1 - 1);
+    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 0, abs_bits(acc.dmax));
+    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 2, abs_bits(ymax));
   }
 }
 
@@ -809,25 +785,11 @@ __global__ __launch_bounds__(64) void k_fsk_split_bwd(double* __restrict__ zd, F
 #pragma unroll
   for (int i = 0; i < 7; ++i) { b[i] = f.b[tone][i]; a[i] = f.a[tone][i]; }
   const double* __restrict__ y1 = sp.y1 + ((size_t)s * 2 + tone) * m1;
-  int64_t k = o0 - sp.w;
-  if (sp.conv) {   // FS0's start state
-    k = o0;
-    const double* zs = sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = zs[i];
-  } else if (k <= 0) {
-    k = 0;
-    const double yl = y1[m1 - 1];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = f.zi[tone][i] * yl;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) z[i] = 0.0;
-  }
-  [[maybe_unused]] double dmax = 0.0, dsum = 0.0;   // ST: the largest step bound, block sums
-  [[maybe_unused]] int dcnt = 0;
-  [[maybe_unused]] double* dblk = ST ? fsk_strict_row(sp, s, tone) + fsk_strict_off_d2(sp) : nullptr;
-  [[maybe_unused]] const double kx = ST ? sp.sb[tone].kx : 0.0, ky = ST ? sp.sb[tone].ky : 0.0;
+  const int64_t k = split_chunk_start(z, sp.conv ? sp.zs + (((size_t)s * 2 + tone) * sp.c + c) * 6 : nullptr,
+                                      f.zi[tone], [&] { return y1[m1 - 1]; }, o0, sp.w);
+  // ST: this chunk's step bounds (D2 blocks, the largest)
+  [[maybe_unused]] StepBound acc{ST ? sp.sb[tone].kx : 0.0, ST ? sp.sb[tone].ky : 0.0,
+                                ST ? fsk_strict_row(sp, s, tone) + strict_off_d2(sp.rows) : nullptr};
   split_chain_2(
       k, o0, o1, bwd_blocks(y1, m1 - 1), [&](int64_t kk) { return y1[m1 - 1 - kk]; },
       [&](int64_t, double v) { fsk_split_warm(z, b, a, v); },
@@ -837,141 +799,34 @@ __global__ __launch_bounds__(64) void k_fsk_split_bwd(double* __restrict__ zd, F
         const double y = fsk_step<MODE>(z, b, a, v);
         const int64_t i = m1 - 1 - kk - pad;
         if (i >= 0 && i < n) zd[((size_t)s * n + fsk_zoff<LIVE>(p, i)) * 2 + tone] = y;
-        if constexpr (ST) {
-          const double dd = __builtin_fma(sp.u2, sz, __builtin_fma(kx, fabs(v), ky * fabs(y)));
-          dmax = fmax(dmax, dd);
-          dsum += dd;
-          if (++dcnt == kStrictBlk) {
-            dblk[kk / kStrictBlk] = dsum;
-            dsum = 0.0;
-            dcnt = 0;
-          }
-        }
+        if constexpr (ST) acc.add(sz, v, y, kk);
       });
   if constexpr (ST) {
-    if (dcnt > 0) dblk[(o1 - 1) / kStrictBlk] = dsum;
-    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 3, fsk_abs_bits(dmax));
+    acc.finish(o1 - 1);
+    atomicMax(sp.bnd + ((size_t)s * 2 + tone) * 8 + 3, abs_bits(acc.dmax));
   }
 }
 
-// KF1 / KF2 (STRICT; split_strict.h, as the PSK split's KB1 / KB2 per tone):
-// thread = (forward block J, stream, tone) -- grid.y = 2 s + tone.
-//   E1[J]  the forward pass's error at output block J: both paths' rounding
-//          (block sums of D through W, the cut remainder at max D), the chunk
-//          starts' errors (+ truncation tk * peak) through GS;
-//   E2[J]  the backward pass's at forward block J: pass 1's rounding through
-//          pass 2 (K12), the start errors through |h| (HS), the last input's
-//          error through the zi start (TZ), its own rounding and starts.
-// max E2 = F bounds |z_split - z_serial| on every sample of the tone while the
-// a-posteriori caps hold (each pass's difference <= 2^-10 of its input peak).
-constexpr int kKfThreads = 256;
-constexpr double kKfTwo = 2.0 + 0x1p-20;
-struct KfRow {
-  double* row;
-  unsigned long long* bw;
-  double D1m, y1m, D2m, peak1, cap1, p2, cap2, c1;
-};
-__device__ __forceinline__ KfRow kf_row(const FskSplit& sp, int64_t s, int tone) {
-  const StrictBp& d = sp.sb[tone];
-  KfRow k;
-  k.row = fsk_strict_row(sp, s, tone);
-  k.bw = sp.bnd + ((size_t)s * 2 + tone) * 8;
-  k.D1m = __longlong_as_double((long long)k.bw[0]);
-  k.y1m = __longlong_as_double((long long)k.bw[2]);
-  k.D2m = __longlong_as_double((long long)k.bw[3]);
-  k.peak1 = __longlong_as_double((long long)sp.peak[s]);
-  k.cap1 = 0x1p-10 * k.peak1;
-  k.p2 = k.y1m + k.cap1;
-  k.cap2 = 0x1p-10 * k.p2;
-  const double sec1 = sp.u2 * d.zb * k.cap1 + d.ky * k.cap1;
-  k.c1 = d.g1x * (sec1 + 2 * 0x1p-1060) + d.gmax * 0x1p-53 * d.zi_sum * k.peak1;
-  return k;
+// KF1 / KF2 (STRICT; split_bound.h KB1 / KB2 per tone): thread = (forward
+// block J, stream, tone) -- grid.y = 2 s + tone.  max E2 = F (bnd slot 6)
+// bounds |z_split - z_serial| on every sample of the tone while the caps hold.
+__device__ __forceinline__ StrictRow kf_strict_row(const FskSplit& sp, int64_t s, int tone) {
+  return strict_row(sp.sb[tone], sp.rows, sp.bnd, s * 2 + tone, sp.peak[s]);
 }
-__device__ __forceinline__ void kf_wave_max(unsigned long long* m, double v, bool live) {
-  unsigned long long x = live ? fsk_abs_bits(v) : 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long y = __shfl_xor(x, o);
-    x = y > x ? y : x;
-  }
-  if ((threadIdx.x & 63) == 0 && x != 0ull) atomicMax(m, x);
-}
-__global__ __launch_bounds__(kKfThreads) void k_fsk_strict_e1(FskSplit sp) {
-  const int64_t s = blockIdx.y >> 1;
+__global__ __launch_bounds__(kKbThreads) void k_fsk_strict_e1(FskSplit sp) {
   const int tone = (int)(blockIdx.y & 1);
-  const int64_t J = (int64_t)blockIdx.x * kKfThreads + threadIdx.x;
-  const StrictBp& d = sp.sb[tone];
-  const KfRow k = kf_row(sp, s, tone);
-  const int64_t LB = sp.L / kStrictBlk;
-  const double* d1 = k.row;
-  const double* ds1 = k.row + fsk_strict_off_ds1(sp);
-  double e = 0.0, st = 0.0;
-  const bool live = J < sp.nb1;
-  if (live) {
-    double r = d.w_tail * k.D1m;
-    const int64_t dn = J + 1 < d.nw ? J + 1 : d.nw;
-#pragma unroll 8
-    for (int64_t dl = 0; dl < dn; ++dl) r = __builtin_fma(d.W[dl], d1[J - dl], r);
-    const int64_t c = J / LB;
-    const int64_t q = J - c * LB;
-    st = c > 0 ? (q < 64 ? d.GS[q] : d.gmax) * (ds1[c] + d.tk * k.peak1) : 0.0;
-    e = kKfTwo * r + k.c1 + st;
-    k.row[fsk_strict_off_s1(sp) + J] = st;
-    k.row[fsk_strict_off_e1(sp) + J] = e;
-  }
-  kf_wave_max(k.bw + 1, e, live);
-  kf_wave_max(k.bw + 4, st, live);
+  const int64_t J = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
+  const StrictRow k = kf_strict_row(sp, blockIdx.y >> 1, tone);
+  const StrictE1 o = strict_e1_block(sp.sb[tone], sp.rows, k, J, sp.L / kStrictBlk);
+  wave_max_to(k.bw + 1, o.e, J < sp.rows.nb1);
+  wave_max_to(k.bw + 4, o.st, J < sp.rows.nb1);
 }
-__global__ __launch_bounds__(kKfThreads) void k_fsk_strict_e2(FskParams p, FskSplit sp) {
-  const int64_t s = blockIdx.y >> 1;
+__global__ __launch_bounds__(kKbThreads) void k_fsk_strict_e2(FskParams p, FskSplit sp) {
   const int tone = (int)(blockIdx.y & 1);
-  const int64_t J = (int64_t)blockIdx.x * kKfThreads + threadIdx.x;
-  const StrictBp& d = sp.sb[tone];
-  const KfRow k = kf_row(sp, s, tone);
-  const int64_t nb1 = sp.nb1, m1 = p.n + 2 * (int64_t)p.pad, LB = sp.L / kStrictBlk;
-  const double* d1 = k.row;
-  const double* d2 = k.row + fsk_strict_off_d2(sp);
-  const double* ds2 = k.row + fsk_strict_off_ds2(sp);
-  const double* e1 = k.row + fsk_strict_off_e1(sp);
-  const double* s1 = k.row + fsk_strict_off_s1(sp);
-  const double E1max = __longlong_as_double((long long)k.bw[1]), S1max = __longlong_as_double((long long)k.bw[4]);
-  const double E1last = fmax(e1[nb1 - 1], nb1 > 1 ? e1[nb1 - 2] : 0.0);
-  const double sec2 = sp.u2 * d.zb * k.cap2 + d.kx * E1max + d.ky * k.cap2;
-  const double c2 = d.hz * k.c1 + d.g1x * (sec2 + 2 * 0x1p-1060) + 2.0 * d.gmax * 0x1p-53 * d.zi_sum * k.p2;
-  auto own2 = [&](int64_t K) {
-    if (K < 0 || K >= nb1) return 0.0;
-    double r = d.w_tail * k.D2m;
-    const int64_t dn = K + 1 < d.nw ? K + 1 : d.nw;
-#pragma unroll 8
-    for (int64_t dl = 0; dl < dn; ++dl) r = __builtin_fma(d.W[dl], d2[K - dl], r);
-    const int64_t c = K / LB;
-    const int64_t q = K - c * LB;
-    const double st = c > 0 ? (q < 64 ? d.GS[q] : d.gmax) * (ds2[c] + d.tk * k.p2) : 0.0;
-    return kKfTwo * r + st;
-  };
-  auto tzw = [&](int64_t q) { return q < d.nz ? d.TZ[q] : d.tz_tail; };
-  double e = 0.0;
-  const bool live = J < nb1;
-  if (live) {
-    double a = d.k12_tail * k.D1m;
-    // the taps whose block lies inside the pass, in the same (ascending) order
-    const int64_t klo = d.k12_off - J > 0 ? d.k12_off - J : 0;
-    const int64_t khi = nb1 - J + d.k12_off < d.nk ? nb1 - J + d.k12_off : d.nk;
-#pragma unroll 8
-    for (int64_t kq = klo; kq < khi; ++kq) a = __builtin_fma(d.K12[kq], d1[J + kq - d.k12_off], a);
-    double h = d.hs_tail * S1max;
-    const int64_t hhi = nb1 - J < d.nh ? nb1 - J : d.nh;
-#pragma unroll 8
-    for (int64_t db = 0; db < hhi; ++db) h = __builtin_fma(d.HS[db], s1[J + db], h);
-    const int64_t jhi = 16 * J + 15 < m1 - 1 ? 16 * J + 15 : m1 - 1;
-    const int64_t k2lo = m1 - 1 - jhi, k2hi = m1 - 1 - 16 * J;
-    const int64_t Ka = k2lo / kStrictBlk, Kb = k2hi / kStrictBlk;
-    const double tz = fmax(tzw(Ka), tzw(Kb)) * E1last;
-    const double o2 = fmax(own2(Ka), own2(Kb));
-    e = kKfTwo * a + h + tz + o2 + c2;
-    k.row[fsk_strict_off_e2(sp) + J] = e;
-  }
-  kf_wave_max(k.bw + 6, e, live);
+  const int64_t J = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
+  const StrictRow k = kf_strict_row(sp, blockIdx.y >> 1, tone);
+  const double e = strict_e2_block(sp.sb[tone], sp.rows, k, J, sp.L / kStrictBlk, p.n + 2 * (int64_t)p.pad);
+  wave_max_to(k.bw + 6, e, J < sp.rows.nb1);
 }
 
 // FS3: per stream, F2's margin scale from the input peak with the split's
@@ -987,8 +842,8 @@ __global__ __launch_bounds__(64) void k_fsk_split_amb(int64_t n_streams, FskPara
   if (sp.strict && peak != 0.0) {   // (an all-zero stream: exact zeros on both paths, never flagged)
     double F = 0.0;
     for (int t = 0; t < 2; ++t) {
-      const KfRow k = kf_row(sp, s, t);
-      const double E1max = __longlong_as_double((long long)k.bw[1]), Fm = __longlong_as_double((long long)k.bw[6]);
+      const StrictRow k = kf_strict_row(sp, s, t);
+      const double E1max = bnd_get(k.bw, 1), Fm = bnd_get(k.bw, 6);
       ok = ok && E1max <= k.cap1 && Fm <= k.cap2;   // false for NaN
       F = fmax(F, Fm);
     }
@@ -1023,9 +878,9 @@ static hipError_t launch_fsk_split_t(int dtype, const void* x, int64_t x_stride,
   if (p.lc.on) hipLaunchKernelGGL((k_fsk_split_bwd<MODE, true, ST>), g, blk, 0, st, zd, p, f, sp);
   else hipLaunchKernelGGL((k_fsk_split_bwd<MODE, false, ST>), g, blk, 0, st, zd, p, f, sp);
   if constexpr (ST) {
-    const dim3 gk((unsigned)((sp.nb1 + kKfThreads - 1) / kKfThreads), (unsigned)(2 * B));
-    hipLaunchKernelGGL(k_fsk_strict_e1, gk, dim3(kKfThreads), 0, st, sp);
-    hipLaunchKernelGGL(k_fsk_strict_e2, gk, dim3(kKfThreads), 0, st, p, sp);
+    const dim3 gk((unsigned)((sp.rows.nb1 + kKbThreads - 1) / kKbThreads), (unsigned)(2 * B));
+    hipLaunchKernelGGL(k_fsk_strict_e1, gk, dim3(kKbThreads), 0, st, sp);
+    hipLaunchKernelGGL(k_fsk_strict_e2, gk, dim3(kKbThreads), 0, st, p, sp);
   }
   if (p.amb) hipLaunchKernelGGL(k_fsk_split_amb, dim3((unsigned)((B + 63) / 64)), blk, 0, st, B, p, sp);
   return hipGetLastError();
@@ -1177,7 +1032,7 @@ hipError_t launch_fsk_split(int dtype, const void* x, int64_t x_stride, int64_t 
   const int mode = fsk_step_mode(f, false);
   if (sp.strict) {
     // the strict bound covers the convolution starts and scipy's step order only
-    if (!sp.conv || !sp.sc || !sp.bnd || sp.L % kStrictBlk != 0 || !sp.sb[0].kabs || !sp.sb[1].kabs)
+    if (!sp.conv || !sp.rows.sc || !sp.bnd || sp.L % kStrictBlk != 0 || !sp.sb[0].kabs || !sp.sb[1].kabs)
       return hipErrorInvalidValue;
     if (mode == 3) return launch_fsk_split_t<3, true>(dtype, x, x_stride, B, z, p, f, sp, st);
     return mode == 1 ? launch_fsk_split_t<1, true>(dtype, x, x_stride, B, z, p, f, sp, st)

@@ -55,8 +55,8 @@
 //   KS3 k_split_lp_fwd   lane = (chunk, component): f * lo, odd ext -> y3 [B][2][m2]
 //   KS4 k_split_lp_bwd   y3 reversed -> symbol samples sym [B][S][2]
 //   KB1-KB4 k_split_strict_e1 / _e2 / _x / _e (strict mode only; thread =
-//                        (block or symbol, stream)): the block step bounds ->
-//                        per-symbol bound e [B][S]
+//                        (block or symbol, stream); KB1 / KB2: split_bound.h):
+//                        the block step bounds -> per-symbol bound e [B][S]
 //   KS5 k_split_slice    thread = (stream, word): numpy's fma differential
 //                        product, the sector / sign decision, the margin
 //                        check -> words, flag, count
@@ -70,6 +70,7 @@
 
 #include "amr_internal.h"
 #include "psk_common.h"
+#include "split_bound.h"
 #include "split_chain.h"
 
 namespace amr {
@@ -90,19 +91,15 @@ __device__ __forceinline__ double split_lp_step(double (&z)[4], const Iir& f, do
   else return df2t_step<4>(z, f, x);
 }
 
-// STRICT (split_strict.h): the rounding one DF-II-T step of scipy's order
-// commits, summed over states, bounded from its pre-step states z1..z7, its
-// input and its output: u2 sum_{i>=1} |z_i| + kx |x| + ky |y|
+// STRICT (split_bound.h StepBound): the pre-step states' sum_{i>=1} |z_i| of
+// one band-pass step, z1..z7 in this pairing
 __device__ __forceinline__ double step_bound_pre(const double (&z)[8]) {
   return ((fabs(z[1]) + fabs(z[2])) + (fabs(z[3]) + fabs(z[4]))) + ((fabs(z[5]) + fabs(z[6])) + fabs(z[7]));
 }
-__device__ __forceinline__ double step_bound(const PskSplit& sp, double sz, double x, double y) {
-  return __builtin_fma(sp.u2, sz, __builtin_fma(sp.kx, fabs(x), sp.ky * fabs(y)));
-}
-
-// |v| as ordered bits (NaN above inf above every finite value)
-__device__ __forceinline__ unsigned long long abs_bits(double v) {
-  return (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
+// STRICT: stream s's scratch row, and KS0's bound into its slot off
+__device__ __forceinline__ double* strict_sc(const PskSplit& sp, int64_t s) { return sp.rows.sc + s * sp.rows.sstride; }
+__device__ __forceinline__ ConvBound strict_conv_bound(const PskSplit& sp, int64_t s, int64_t off) {
+  return ConvBound{sp.sb.kabs, sp.sb.z0abs, sp.sb.gam, strict_sc(sp, s) + off};
 }
 
 // KS0 (sp.conv): a band-pass chunk's start state without a warm-up.  The
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(256) void k_split_bp_state_fwd(PskBuffers buf, PskP
         return ox.right(j - pad - n);
       },
       sp.zs + (s * sp.c1 + c) * 8,
-      ConvBound{sp.kabs, sp.z0abs, sp.gam, ST ? sp.sc + s * sp.sstride + strict_off_ds1(sp) + c : nullptr});
+      ST ? strict_conv_bound(sp, s, strict_off_ds1(sp.rows) + c) : ConvBound{});
 }
 
 template <bool ST>
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(256) void k_split_bp_state_bwd(PskBuffers buf, PskP
   split_conv_state<8, ST>(
       sp.ktab, sp.z0tab, sp.w1, c * sp.L, y1[m1 - 1], [&](int64_t k) { return y1[m1 - 1 - k]; },
       sp.zs + (s * sp.c1 + c) * 8,
-      ConvBound{sp.kabs, sp.z0abs, sp.gam, ST ? sp.sc + s * sp.sstride + strict_off_ds2(sp) + c : nullptr});
+      ST ? strict_conv_bound(sp, s, strict_off_ds2(sp.rows) + c) : ConvBound{});
 }
 
 // KS1: the band-pass's forward pass over ext(x) (odd extension in the input's
@@ -162,41 +159,19 @@ __global__ __launch_bounds__(64) void k_split_bp_fwd(PskBuffers buf, PskParams p
   const int64_t o0 = c * sp.L, o1 = o0 + sp.L < m1 ? o0 + sp.L : m1;
   const OddExt<T> ox(x, buf.edge, s, n, pad);
   double z[8];
-  int64_t j = o0 - sp.w1;
-  if (sp.conv) {   // KS0's start state
-    j = o0;
-    const double* zs = sp.zs + (s * sp.c1 + c) * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = zs[i];
-  } else if (j <= 0) {
-    j = 0;
-    const double e0 = ox.left(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = f.zi[i] * e0;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = 0.0;
-  }
+  int64_t j = split_chunk_start(z, sp.conv ? sp.zs + (s * sp.c1 + c) * 8 : nullptr, f.zi,
+                                [&] { return ox.left(0); }, o0, sp.w1);
   double* __restrict__ y1 = sp.y1 + s * m1;
   unsigned long long pk = 0;
-  // ST: this chunk's largest step bound and |y1|, and the step bounds summed
-  // per block of kStrictBlk outputs (chunks start on block boundaries)
-  [[maybe_unused]] double dmax = 0.0, ymax = 0.0, dsum = 0.0;
-  [[maybe_unused]] int dcnt = 0;
-  [[maybe_unused]] double* dblk = ST ? sp.sc + s * sp.sstride + strict_off_d1(sp) : nullptr;
+  // ST: this chunk's step bounds (D1 blocks, the largest) and largest |y1|
+  [[maybe_unused]] StepBound acc{sp.sb.kx, sp.sb.ky, ST ? strict_sc(sp, s) + strict_off_d1(sp.rows) : nullptr};
+  [[maybe_unused]] double ymax = 0.0;
   auto out = [&](int64_t jj, double e) {
     if constexpr (ST) {
       const double sz = step_bound_pre(z);
       const double y = split_bp_step<ZO>(z, f, e);
       y1[jj] = y;
-      const double dd = step_bound(sp, sz, e, y);
-      dmax = fmax(dmax, dd);
-      dsum += dd;
-      if (++dcnt == kStrictBlk) {
-        dblk[jj / kStrictBlk] = dsum;
-        dsum = 0.0;
-        dcnt = 0;
-      }
+      acc.add(sz, e, y, jj);
       ymax = fmax(ymax, fabs(y));                 // (NaN / inf input: the peak test flags the stream)
     } else {
       y1[jj] = split_bp_step<ZO>(z, f, e);
@@ -221,8 +196,8 @@ __global__ __launch_bounds__(64) void k_split_bp_fwd(PskBuffers buf, PskParams p
   for (; j < o1; ++j) body(j, ox.right(j - pad - n));
   atomicMax(&sp.peak[s], pk);
   if constexpr (ST) {
-    if (dcnt > 0) dblk[(o1 - 1) / kStrictBlk] = dsum;   // the pass's last, partial block
-    atomicMax(sp.bnd + s * 8 + 0, abs_bits(dmax));
+    acc.finish(o1 - 1);
+    atomicMax(sp.bnd + s * 8 + 0, abs_bits(acc.dmax));
     atomicMax(sp.bnd + s * 8 + 2, abs_bits(ymax));
   }
 }
@@ -241,24 +216,11 @@ __global__ __launch_bounds__(64) void k_split_bp_bwd(PskBuffers buf, PskParams p
   double* __restrict__ fo = sp.f + s * n;
   const int64_t o0 = c * sp.L, o1 = o0 + sp.L < m1 ? o0 + sp.L : m1;
   double z[8];
-  int64_t k = o0 - sp.w1;
-  if (sp.conv) {   // KS0's start state
-    k = o0;
-    const double* zs = sp.zs + (s * sp.c1 + c) * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = zs[i];
-  } else if (k <= 0) {
-    k = 0;
-    const double yl = y1[m1 - 1];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = f.zi[i] * yl;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = 0.0;
-  }
-  [[maybe_unused]] double dmax = 0.0, fmx = 0.0, dsum = 0.0;   // ST: the largest step bound and |f|, block sums
-  [[maybe_unused]] int dcnt = 0;
-  [[maybe_unused]] double* dblk = ST ? sp.sc + s * sp.sstride + strict_off_d2(sp) : nullptr;
+  const int64_t k = split_chunk_start(z, sp.conv ? sp.zs + (s * sp.c1 + c) * 8 : nullptr, f.zi,
+                                      [&] { return y1[m1 - 1]; }, o0, sp.w1);
+  // ST: this chunk's step bounds (D2 blocks, the largest) and largest |f|
+  [[maybe_unused]] StepBound acc{sp.sb.kx, sp.sb.ky, ST ? strict_sc(sp, s) + strict_off_d2(sp.rows) : nullptr};
+  [[maybe_unused]] double fmx = 0.0;
   split_chain_2(
       k, o0, o1, bwd_blocks(y1, m1 - 1), [&](int64_t kk) { return y1[m1 - 1 - kk]; },
       [&](int64_t, double v) { split_bp_warm<ZO>(z, f, v); },
@@ -271,20 +233,11 @@ __global__ __launch_bounds__(64) void k_split_bp_bwd(PskBuffers buf, PskParams p
           fo[i] = y;
           if constexpr (ST) fmx = fmax(fmx, fabs(y));
         }
-        if constexpr (ST) {
-          const double dd = step_bound(sp, sz, v, y);
-          dmax = fmax(dmax, dd);
-          dsum += dd;
-          if (++dcnt == kStrictBlk) {
-            dblk[kk / kStrictBlk] = dsum;
-            dsum = 0.0;
-            dcnt = 0;
-          }
-        }
+        if constexpr (ST) acc.add(sz, v, y, kk);
       });
   if constexpr (ST) {
-    if (dcnt > 0) dblk[(o1 - 1) / kStrictBlk] = dsum;
-    atomicMax(sp.bnd + s * 8 + 3, abs_bits(dmax));
+    acc.finish(o1 - 1);
+    atomicMax(sp.bnd + s * 8 + 3, abs_bits(acc.dmax));
     atomicMax(sp.bnd + s * 8 + 5, abs_bits(fmx));
   }
 }
@@ -310,16 +263,7 @@ __global__ __launch_bounds__(64) void k_split_lp_fwd(PskBuffers buf, PskParams p
   const double xl = Xm(n - 1);
   const int64_t o0 = c * sp.L, o1 = o0 + sp.L < m2 ? o0 + sp.L : m2;
   double z[4];
-  int64_t j = o0 - sp.w2;
-  if (j <= 0) {
-    j = 0;
-    const double e0 = 2.0 * x0 - Xm(pad);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = f.zi[i] * e0;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = 0.0;
-  }
+  int64_t j = split_chunk_start(z, nullptr, f.zi, [&] { return 2.0 * x0 - Xm(pad); }, o0, sp.w2);
   double* __restrict__ y3 = sp.y3 + ((size_t)s * 2 + comp) * m2;
   auto body = [&](int64_t jj, double e) {
     const double y = split_lp_step<SYM>(z, f, e);
@@ -360,16 +304,7 @@ __global__ __launch_bounds__(64) void k_split_lp_bwd(PskBuffers buf, PskParams p
   double* __restrict__ so = sp.sym + (size_t)s * S * 2 + comp;
   const int64_t o0 = c * sp.L, o1 = o0 + sp.L < m2 ? o0 + sp.L : m2;
   double z[4];
-  int64_t k = o0 - sp.w2;
-  if (k <= 0) {
-    k = 0;
-    const double yl = y3[m2 - 1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = f.zi[i] * yl;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = 0.0;
-  }
+  const int64_t k = split_chunk_start(z, nullptr, f.zi, [&] { return y3[m2 - 1]; }, o0, sp.w2);
   // over the outputs, sample i = m2 - 1 - k - pad falls by one per step:
   // r = (i - first) mod sps counts down to the next symbol sample
   const int64_t i0 = m2 - 1 - (k > o0 ? k : o0) - pad;
@@ -389,150 +324,42 @@ __global__ __launch_bounds__(64) void k_split_lp_bwd(PskBuffers buf, PskParams p
 // streams; the per-stream maxima meet in bnd's free slots by atomicMax) turn
 // KS0-KS2's per-block step bounds and per-chunk start bounds into a bound e(k)
 // on each symbol component's |split - reference|:
-//   KB1 E1[J]  the forward pass, output block J: the split's and the serial's
-//              rounding (block sums of D through W, the cut remainder at max D),
-//              the chunk starts' errors (+ truncation tk * peak) through GS
-//   KB2 E2[J]  the backward pass at forward block J: the forward rounding
-//              through the backward pass (K12, exact at block resolution), the
-//              start errors through |h| (HS), the last input's error through the
-//              zi start (TZ), its own rounding and starts (in its own block index)
+//   KB1 E1[J], KB2 E2[J]  the band-pass's forward and backward pass at output
+//              block J (split_bound.h strict_e1_block / strict_e2_block)
 //   KB3 X[fb]  the mixer's output error over sample block fb
 //   KB4 e(k)   the symbol's complex error: lpc[k] x the largest X within the
 //              low-pass's reach of symbol k (and the extension's source blocks)
 //              + the cut remainder (one complex sum through the unit-modulus
 //              mixer), + sqrt2 x the per-component roundings (mixer, c3 P3)
-// The serial's rounding is the split's within the a-posteriori caps (each
-// pass's difference <= 2^-10 of its input peak; a stream past them gets e =
-// inf: flagged).  Every sum is of non-negative terms; the final factor
-// 1 + 2^-30 covers their own rounding.  (Round 6's first cut ran all four in
-// one workgroup per stream: 1.05 ms of a 1.4 ms strict one-capture call.)
-__device__ __forceinline__ double bnd_get(const unsigned long long* b, int i) {
-  return __longlong_as_double((long long)b[i]);
+// A stream past the a-posteriori caps gets e = inf: flagged.  The final factor
+// 1 + 2^-30 covers the sums' own rounding.
+__device__ __forceinline__ StrictRow kb_row(const PskSplit& sp, int64_t s) {
+  return strict_row(sp.sb, sp.rows, sp.bnd, s, sp.peak[s]);
 }
-constexpr int kKbThreads = 256;
-// bnd slots: 0 D1max, 1 E1max (KB1), 2 max|y1|, 3 D2max, 4 S1max (KB1),
-// 5 max|f|, 6 Fmax (KB2), 7 Xmax (KB3)
-struct KbStream {
-  double* sc;
-  const unsigned long long* b;
-  unsigned long long* bw;
-  double D1m, y1m, D2m, fm0, peak1, cap1, p2, cap2, c1;
-};
-__device__ __forceinline__ KbStream kb_stream(const PskSplit& sp, int64_t s) {
-  KbStream k;
-  k.sc = sp.sc + s * sp.sstride;
-  k.bw = sp.bnd + s * 8;
-  k.b = k.bw;
-  k.D1m = bnd_get(k.b, 0);
-  k.y1m = bnd_get(k.b, 2);
-  k.D2m = bnd_get(k.b, 3);
-  k.fm0 = bnd_get(k.b, 5);
-  k.peak1 = __longlong_as_double((long long)sp.peak[s]);
-  k.cap1 = 0x1p-10 * k.peak1;
-  k.p2 = k.y1m + k.cap1;
-  k.cap2 = 0x1p-10 * k.p2;
-  const double sec1 = sp.u2 * sp.zb * k.cap1 + sp.ky * k.cap1;
-  // the forward pass's per-stream terms (besides the block sums)
-  k.c1 = sp.g1x * (sec1 + 2 * 0x1p-1060) + sp.gmax * 0x1p-53 * sp.zi_sum * k.peak1;
-  return k;
-}
-// a wave's maximum of non-negative v into *m (one atomic per wave)
-__device__ __forceinline__ void wave_max_to(unsigned long long* m, double v, bool live) {
-  unsigned long long x = live ? (unsigned long long)__double_as_longlong(fabs(v)) : 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long y = __shfl_xor(x, o);
-    x = y > x ? y : x;
-  }
-  if ((threadIdx.x & 63) == 0 && x != 0ull) atomicMax(m, x);
-}
-constexpr double kKbTwo = 2.0 + 0x1p-20;
 
 __global__ __launch_bounds__(kKbThreads) void k_split_strict_e1(PskParams p, PskSplit sp) {
-  const int64_t s = blockIdx.y;
   const int64_t J = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
-  const KbStream k = kb_stream(sp, s);
-  const int64_t nb1 = sp.nb1, LB = sp.L / kStrictBlk;
-  const double* d1 = k.sc + strict_off_d1(sp);
-  const double* ds1 = k.sc + strict_off_ds1(sp);
-  double e = 0.0, st = 0.0;
-  const bool live = J < nb1;
-  if (live) {
-    double r = sp.w_tail * k.D1m;
-    const int64_t dn = J + 1 < sp.nw ? J + 1 : sp.nw;
-#pragma unroll 8
-    for (int64_t dl = 0; dl < dn; ++dl) r = __builtin_fma(sp.kW[dl], d1[J - dl], r);
-    const int64_t c = J / LB;
-    const int64_t q = J - c * LB;
-    st = c > 0 ? (q < 64 ? sp.kGS[q] : sp.gmax) * (ds1[c] + sp.tk * k.peak1) : 0.0;
-    e = kKbTwo * r + k.c1 + st;
-    k.sc[strict_off_s1(sp) + J] = st;
-    k.sc[strict_off_e1(sp) + J] = e;
-  }
+  const StrictRow k = kb_row(sp, blockIdx.y);
+  const StrictE1 o = strict_e1_block(sp.sb, sp.rows, k, J, sp.L / kStrictBlk);
   (void)p;
-  wave_max_to(k.bw + 1, e, live);
-  wave_max_to(k.bw + 4, st, live);
+  wave_max_to(k.bw + 1, o.e, J < sp.rows.nb1);
+  wave_max_to(k.bw + 4, o.st, J < sp.rows.nb1);
 }
 
 __global__ __launch_bounds__(kKbThreads) void k_split_strict_e2(PskParams p, PskSplit sp) {
-  const int64_t s = blockIdx.y;
   const int64_t J = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
-  const KbStream k = kb_stream(sp, s);
-  const int64_t nb1 = sp.nb1, m1 = p.m1, LB = sp.L / kStrictBlk;
-  const double* d1 = k.sc + strict_off_d1(sp);
-  const double* d2 = k.sc + strict_off_d2(sp);
-  const double* ds2 = k.sc + strict_off_ds2(sp);
-  const double* e1 = k.sc + strict_off_e1(sp);
-  const double* s1 = k.sc + strict_off_s1(sp);
-  const double E1max = bnd_get(k.b, 1), S1max = bnd_get(k.b, 4);
-  const double E1last = fmax(e1[nb1 - 1], nb1 > 1 ? e1[nb1 - 2] : 0.0);
-  const double sec2 = sp.u2 * sp.zb * k.cap2 + sp.kx * E1max + sp.ky * k.cap2;
-  const double c2 = sp.hz * k.c1 + sp.g1x * (sec2 + 2 * 0x1p-1060) + 2.0 * sp.gmax * 0x1p-53 * sp.zi_sum * k.p2;
-  // the backward pass's own rounding and starts at its block K (its own index)
-  auto own2 = [&](int64_t K) {
-    if (K < 0 || K >= nb1) return 0.0;
-    double r = sp.w_tail * k.D2m;
-    const int64_t dn = K + 1 < sp.nw ? K + 1 : sp.nw;
-#pragma unroll 8
-    for (int64_t dl = 0; dl < dn; ++dl) r = __builtin_fma(sp.kW[dl], d2[K - dl], r);
-    const int64_t c = K / LB;
-    const int64_t q = K - c * LB;
-    const double st = c > 0 ? (q < 64 ? sp.kGS[q] : sp.gmax) * (ds2[c] + sp.tk * k.p2) : 0.0;
-    return kKbTwo * r + st;
-  };
-  auto tzw = [&](int64_t q) { return q < sp.nz ? sp.kTZ[q] : sp.tz_tail; };
-  double e = 0.0;
-  const bool live = J < nb1;
-  if (live) {
-    // forward block J: j in [16 J, 16 J + 15] <-> backward index k2 = m1 - 1 - j
-    double a = sp.k12_tail * k.D1m;
-    // the taps whose block lies inside the pass, in the same (ascending) order
-    const int64_t klo = sp.k12_off - J > 0 ? sp.k12_off - J : 0;
-    const int64_t khi = nb1 - J + sp.k12_off < sp.nk ? nb1 - J + sp.k12_off : sp.nk;
-#pragma unroll 8
-    for (int64_t kq = klo; kq < khi; ++kq) a = __builtin_fma(sp.kK12[kq], d1[J + kq - sp.k12_off], a);
-    double h = sp.hs_tail * S1max;
-    const int64_t hhi = nb1 - J < sp.nh ? nb1 - J : sp.nh;
-#pragma unroll 8
-    for (int64_t db = 0; db < hhi; ++db) h = __builtin_fma(sp.kHS[db], s1[J + db], h);
-    const int64_t jhi = 16 * J + 15 < m1 - 1 ? 16 * J + 15 : m1 - 1;
-    const int64_t k2lo = m1 - 1 - jhi, k2hi = m1 - 1 - 16 * J;
-    const int64_t Ka = k2lo / kStrictBlk, Kb = k2hi / kStrictBlk;
-    const double tz = fmax(tzw(Ka), tzw(Kb)) * E1last;
-    const double o2 = fmax(own2(Ka), own2(Kb));
-    e = kKbTwo * a + h + tz + o2 + c2;
-    k.sc[strict_off_e2(sp) + J] = e;
-  }
-  wave_max_to(k.bw + 6, e, live);
+  const StrictRow k = kb_row(sp, blockIdx.y);
+  const double e = strict_e2_block(sp.sb, sp.rows, k, J, sp.L / kStrictBlk, p.m1);
+  wave_max_to(k.bw + 6, e, J < sp.rows.nb1);
 }
 
 __global__ __launch_bounds__(kKbThreads) void k_split_strict_x(PskParams p, PskSplit sp) {
   const int64_t s = blockIdx.y;
   const int64_t fb = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
-  const KbStream k = kb_stream(sp, s);
+  const StrictRow k = kb_row(sp, s);
   const int64_t n = p.n;
-  const double* e2 = k.sc + strict_off_e2(sp);
-  const double fm = k.fm0 + bnd_get(k.b, 6);
+  const double* e2 = k.sc + strict_off_e2(sp.rows);
+  const double fm = bnd_get(k.bw, 5) + bnd_get(k.bw, 6);
   double x = 0.0;
   const bool live = fb < sp.nbs;
   if (live) {
@@ -547,12 +374,12 @@ __global__ __launch_bounds__(kKbThreads) void k_split_strict_x(PskParams p, PskS
 __global__ __launch_bounds__(kKbThreads) void k_split_strict_e(PskParams p, PskSplit sp) {
   const int64_t s = blockIdx.y;
   const int64_t kk = (int64_t)blockIdx.x * kKbThreads + threadIdx.x;
-  const KbStream k = kb_stream(sp, s);
+  const StrictRow k = kb_row(sp, s);
   const int64_t n = p.n, nbs = sp.nbs, S = p.n_sym;
   const double* xb = k.sc + strict_off_x(sp);
   double* eo = k.sc + strict_off_e(sp);
-  const double E1max = bnd_get(k.b, 1), Fmax = bnd_get(k.b, 6), Xmax = bnd_get(k.b, 7);
-  const double fm = k.fm0 + Fmax;
+  const double E1max = bnd_get(k.bw, 1), Fmax = bnd_get(k.bw, 6), Xmax = bnd_get(k.bw, 7);
+  const double fm = bnd_get(k.bw, 5) + Fmax;
   const double P3 = 3.0 * (fm + Xmax);
   const bool ok = E1max <= k.cap1 && Fmax <= k.cap2;      // false for NaN
   if (kk < S) {
@@ -613,7 +440,7 @@ __global__ __launch_bounds__(64) void k_split_slice(PskBuffers buf, PskParams p,
   // STRICT: |symbol error|_2 <= e(k) (KB4; inf when the stream's caps failed);
   // else kappa * peak for every symbol
   const double sq2 = 0x1.6a09e667f3bcdp+0;
-  const double* eo = sp.strict ? sp.sc + s * sp.sstride + strict_off_e(sp) : nullptr;
+  const double* eo = sp.strict ? strict_sc(sp, s) + strict_off_e(sp) : nullptr;
   auto esym = [&](int64_t k) { return eo[k]; };
   const double* __restrict__ sy = sp.sym + (size_t)s * S * 2;
   uint32_t word = 0;
@@ -658,7 +485,7 @@ hipError_t launch_psk_split_bp(const PskBuffers& b, const PskParams& p, const Ii
   const bool zo = p.bp_zero_odd && p.bp_sym;
   if (sp.conv && (!sp.ktab || !sp.z0tab || !sp.zs)) return hipErrorInvalidValue;
   // the strict bound covers the convolution starts only (no FMA warm-ups)
-  if (sp.strict && (!sp.conv || !sp.bnd || !sp.kabs || !sp.z0abs || !sp.lpc)) return hipErrorInvalidValue;
+  if (sp.strict && (!sp.conv || !sp.bnd || !sp.sb.kabs || !sp.sb.z0abs || !sp.lpc)) return hipErrorInvalidValue;
   const bool stv = sp.strict != 0;
 #define KS0F(T) \
   do { \
@@ -729,10 +556,10 @@ hipError_t launch_psk_split_slice(const PskBuffers& b, const PskParams& p, const
   if (B > 65535) return hipErrorInvalidValue;
   const dim3 blk(64), g5((unsigned)((p.n_words + 63) / 64), (unsigned)B);
   if (sp.strict) {
-    if (!sp.sc || sp.L % kStrictBlk != 0) return hipErrorInvalidValue;
+    if (!sp.rows.sc || sp.L % kStrictBlk != 0) return hipErrorInvalidValue;
     auto g = [&](int64_t units) { return dim3((unsigned)((units + kKbThreads - 1) / kKbThreads), (unsigned)B); };
-    hipLaunchKernelGGL(k_split_strict_e1, g(sp.nb1), dim3(kKbThreads), 0, st, p, sp);
-    hipLaunchKernelGGL(k_split_strict_e2, g(sp.nb1), dim3(kKbThreads), 0, st, p, sp);
+    hipLaunchKernelGGL(k_split_strict_e1, g(sp.rows.nb1), dim3(kKbThreads), 0, st, p, sp);
+    hipLaunchKernelGGL(k_split_strict_e2, g(sp.rows.nb1), dim3(kKbThreads), 0, st, p, sp);
     hipLaunchKernelGGL(k_split_strict_x, g(sp.nbs), dim3(kKbThreads), 0, st, p, sp);
     hipLaunchKernelGGL(k_split_strict_e, g(p.n_sym), dim3(kKbThreads), 0, st, p, sp);
   }

@@ -67,6 +67,30 @@ __device__ __forceinline__ void split_chain_2(int64_t j0, int64_t o0, int64_t j1
   split_chain_run(j0 > o0 ? j0 : o0, j1, blk, one, out);
 }
 
+// A chunk's start state z and the index its run begins at, for outputs from
+// o0: the convolution state zs (KS0 / FS0; null where the pass has none) and
+// o0 itself; else, w samples early from a zero state -- or, for a chunk that
+// reaches the pass's start, scipy's zi * v0() from index 0 (v0: the pass's
+// first value, evaluated by those chunks alone).
+template <int NS, typename V0>
+__device__ __forceinline__ int64_t split_chunk_start(double (&z)[NS], const double* zs, const double* zi, V0 v0,
+                                                     int64_t o0, int64_t w) {
+  if (zs) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) z[i] = zs[i];
+    return o0;
+  }
+  if (o0 - w <= 0) {
+    const double e0 = v0();
+#pragma unroll
+    for (int i = 0; i < NS; ++i) z[i] = zi[i] * e0;
+    return 0;
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) z[i] = 0.0;
+  return o0 - w;
+}
+
 // blocks of a forward run over a[0..): values cvt(a[j]) for j in [j, j + K)
 template <typename T, typename Cvt>
 __device__ __forceinline__ auto fwd_blocks(const T* a, Cvt cvt) {

@@ -53,7 +53,7 @@
 
 namespace amr {
 
-// block bound (KB, psk_split_kernels.hip): the per-step bounds D summed over
+// block bound (KB1 / KB2, split_bound.h): the per-step bounds D summed over
 // blocks of kStrictBlk outputs, convolved at block resolution with window
 // maxima of the responses (exact within the block: 1.3x of the per-sample
 // convolution, against 5x for the stream's max D), the responses cut where
@@ -84,6 +84,53 @@ struct StrictDesign {
   double c3 = 0;                 // x the low-pass input peak P3: own rounding, warm-up truncation, extension rounding
   double lp_kx = 0, lp_ky = 0;
 };
+
+// The band-pass design's device tables and the kernels' pointers to them, in
+// the order they are uploaded: appended to a host table (strict_bp_append),
+// and the kernels' view (StrictBp) of such a run of strict_bp_doubles doubles
+// on the device at base (strict_bp_view)
+struct StrictBpTable {
+  std::vector<double> StrictDesign::*host;
+  const double* StrictBp::*dev;
+};
+constexpr StrictBpTable kStrictBpTables[] = {
+    {&StrictDesign::kabs, &StrictBp::kabs}, {&StrictDesign::z0abs, &StrictBp::z0abs}, {&StrictDesign::W, &StrictBp::W},
+    {&StrictDesign::K12, &StrictBp::K12},   {&StrictDesign::HS, &StrictBp::HS},       {&StrictDesign::GS, &StrictBp::GS},
+    {&StrictDesign::TZ, &StrictBp::TZ}};
+inline void strict_bp_append(const StrictDesign& d, std::vector<double>& tab) {
+  for (const StrictBpTable& t : kStrictBpTables) tab.insert(tab.end(), (d.*t.host).begin(), (d.*t.host).end());
+}
+inline size_t strict_bp_doubles(const StrictDesign& d) {
+  size_t n = 0;
+  for (const StrictBpTable& t : kStrictBpTables) n += (d.*t.host).size();
+  return n;
+}
+inline StrictBp strict_bp_view(const StrictDesign& d, const double* base) {
+  StrictBp b{};
+  for (const StrictBpTable& t : kStrictBpTables) {
+    b.*t.dev = base;
+    base += (d.*t.host).size();
+  }
+  b.nw = (int)d.W.size();
+  b.nk = (int)d.K12.size();
+  b.nh = (int)d.HS.size();
+  b.nz = (int)d.TZ.size();
+  b.k12_off = d.k12_off;
+  b.w_tail = d.w_tail;
+  b.k12_tail = d.k12_tail;
+  b.hs_tail = d.hs_tail;
+  b.tz_tail = d.tz_tail;
+  b.gam = d.gam;
+  b.kx = d.kx;
+  b.ky = d.ky;
+  b.g1x = d.g1x;
+  b.gmax = d.gmax;
+  b.hz = d.hz;
+  b.tk = d.tk;
+  b.zi_sum = d.zi_sum;
+  b.zb = d.zb;
+  return b;
+}
 
 namespace strict_detail {
 typedef long double LD;
