@@ -54,7 +54,7 @@ EXPORTS = [
     "amr_comm_synchronize", "amr_comm_allgather_host", "amr_comm_allreduce_max", "amr_comm_world", "amr_tx_samples", "amr_tx_work_bytes", "amr_modulate_host", "amr_modulate_device",
     "amr_resample_host", "amr_hilbert_env_exact_host", "amr_fsk_plan_exact_streams",
     "amr_fsk_plan_set_exact_mode", "amr_psk_plan_set_layout", "amr_psk_plan_split_info", "amr_psk_split_design",
-    "amr_psk_split_symbols_host", "amr_psk_f32_margin", "amr_psk_plan_last_f32f", "amr_split_state_tables",
+    "amr_psk_split_symbols_host", "amr_psk_f32_margin", "amr_psk_plan_last_f32f", "amr_psk_plan_last_lowpass", "amr_split_state_tables",
     "amr_psk_plan_split_conv",
     "amr_fsk_plan_set_layout", "amr_fsk_plan_split_info", "amr_fsk_split_design", "amr_fsk_split_bandpass_host",
     "amr_fsk_fft_margin", "amr_fsk_plan_margin", "amr_fsk_plan_set_split_strict", "amr_fsk_plan_split_strict",
@@ -313,6 +313,7 @@ def lib():
             "amr_psk_plan_split_conv": (I32, [P]),
             "amr_psk_f32_margin": (D, [P, P, I32]),
             "amr_psk_plan_last_f32f": (I32, [P]),
+            "amr_psk_plan_last_lowpass": (I32, [P]),
             "amr_psk_demod_host_async": (I32, [P, P, I32, I64, I64, P, I64, P, P]),
             "amr_fsk_demod_host_async": (I32, [P, P, I32, I64, I64, P, I64, P, P]),
             "amr_host_register": (I32, [P, I64]),
@@ -688,6 +689,12 @@ class PskPlan:
     def last_f32f(self) -> bool:
         """The last call handed the band-pass output to the low-pass in float32."""
         return int(lib().amr_psk_plan_last_f32f(self.handle)) == 1
+
+    LOWPASS = {0: "lane", 1: "lane_fused", 2: "lane_half"}           # AMR_LP_* (include/amr.h)
+
+    def last_lowpass(self) -> str:
+        """The lane layout's low-pass kernel of the last call ("none": it ran no lane low-pass)."""
+        return self.LOWPASS.get(int(lib().amr_psk_plan_last_lowpass(self.handle)), "none")
 
     def split_conv(self) -> bool:
         """The time-split layout starts its band-pass chunks from convolution

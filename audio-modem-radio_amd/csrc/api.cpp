@@ -27,7 +27,7 @@ hipError_t launch_psk_slice(const PskBuffers&, const PskParams&, hipStream_t, bo
 hipError_t launch_psk_bandpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_bandpass_fixup(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 bool psk_lane_fused(const PskBuffers&, const PskParams&);
-hipError_t launch_psk_lowpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t, bool* sliced);
+hipError_t launch_psk_lowpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t, bool* sliced, int* kernel);
 int64_t psk_lane_bp_scratch_doubles(int64_t n_streams, int64_t n, int pad);
 int64_t psk_lane_lp_scratch_doubles(int64_t n_streams, int64_t n, int pad);
 int64_t psk_exact_scratch_bytes(int64_t n_streams, int64_t m2);
@@ -280,6 +280,7 @@ struct amr_psk_plan {
   double* strict_sc = nullptr;    // the per-stream scratch of the block bound (PskSplit::sc), grown per call
   int64_t strict_sc_bytes = 0;
   bool last_f32f = false;       // the last lane-layout call handed f over in float32
+  int last_lowpass = -1;        // AMR_LP_* of the last lane-layout call's low-pass (-1: none ran)
   bool last_strict = false;     // the last split call decided with the strict bound
 };
 
@@ -833,6 +834,7 @@ int amr_psk_split_strict_design(const double* bp_b, const double* bp_a, const do
 }
 
 int amr_psk_plan_last_f32f(const amr_psk_plan* plan) { return plan ? (plan->last_f32f ? 1 : 0) : -1; }
+int amr_psk_plan_last_lowpass(const amr_psk_plan* plan) { return plan ? plan->last_lowpass : -1; }
 
 int amr_split_state_tables(const double* b, const double* a, const double* zi, int nt, int64_t w, double* K,
                            double* Z0) {
@@ -1129,6 +1131,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
   }
   const bool lane = layout == AMR_LAYOUT_LANE;
   pl->last_layout = layout;
+  pl->last_lowpass = -1;
   if (pl->p.n_sym >= 2) {
     // the sizes this layout's kernels assume (the row layout's full-length
     // intermediates are allocated on its first call; the time-split layout
@@ -1239,7 +1242,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     } else {
       // forward + backward low-pass in one kernel: timed in the lowpass_fwd slot
       HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
-      HIP_TRY(launch_psk_lowpass_lane(b, pl->p, pl->lp, st, &sliced));
+      HIP_TRY(launch_psk_lowpass_lane(b, pl->p, pl->lp, st, &sliced, &pl->last_lowpass));
       HIP_TRY(mark(AMR_T_LOWPASS_FWD, 1));
     }
     HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 0));

@@ -31,6 +31,13 @@
 //     B/sample) becomes a second read of f (8 B/sample, mostly L2: the re and
 //     im waves of the same streams run on one XCD) plus 2 B/sample of
 //     checkpoints.  Symbols are written straight from the backward pass.
+//   * low-pass with the slicer fused (from 32768 live streams, static symbol
+//     slots): k_lp_lane_h, both components of 32 streams in one wave -- f is
+//     fetched once per group and pass, the symbol samples go from the
+//     backward pass through a half-wave swap into the slicer, and only the
+//     decided words leave the chip; no LDS symbol ring and no workgroup
+//     barrier.  AMR_LP_HALF=0 keeps the earlier two-wave form (k_lp_lane
+//     FUSE: a component per wave, ring + one barrier per slicing region).
 // A re-run tile executes exactly the operations the forward pass executed,
 // from exactly the same state, so it reproduces its outputs bit for bit.
 #include <math.h>
@@ -38,12 +45,13 @@
 
 #include <type_traits>
 
+#include "amr.h"
 #include "amr_internal.h"
 #include "psk_common.h"
 
 namespace amr {
 
-constexpr int kBpT = 32;     // band-pass checkpoint tile (samples)
+constexpr int kBpT = 32;    // band-pass checkpoint tile (samples)
 constexpr int kLpT = 40;     // low-pass checkpoint tile: a multiple of sps 5 / 10 / 20 (static symbol slots)
 constexpr int kLpT2 = 20;    // the same for the role-split low-pass (LDS: 2 components x 2 buffers x tile)
 
@@ -857,6 +865,278 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
 }
 
 // ---------------------------------------------------------------------------
+// low-pass with the fused slicer, both components in ONE wave (AMR_LP_HALF,
+// the default wherever the fused slicer runs): a wave holds 32 streams, lanes
+// 0-31 their re and lanes 32-63 their im component (lane l and l + 32 are one
+// stream).  A group of 64 streams is still two waves -- split by stream half
+// (the two 512-B runs of f_index) instead of by component -- and a workgroup
+// four waves = two groups, the grid and placement of k_lp_lane<.., 4>.
+// Per lane the arithmetic is k_lp_lane's, in its order: the mixer, lp_step,
+// the tiny_min3 detector, the class checks, forward pass / re-run / backward
+// pass.  What changes is what the waves share:
+//   * f: a wave reads only its half's 512-B runs, lanes l and l + 32 the same
+//     16 B -- each f pair is fetched once per group and pass, not twice.
+//   * the LO multipliers and lo4 are per component, so per lane half: the
+//     per-wave LDS double buffer holds both components' tile (lanes < TL load
+//     one value of each), read back by ds_read_b128 at a half-dependent
+//     address (a broadcast inside each half).
+//   * the slicer runs where a symbol sample is produced: one half-wave swap
+//     (v_permlane32_swap) hands every lane both components, every lane forms
+//     s[k+1] * conj(s[k]), the decision and the MSB-first word exactly as
+//     k_lp_lane's region_done, and lanes 0-31 store the words.  No symbol
+//     ring, no workgroup barrier, no barrier loop for idle groups: the waves
+//     of a workgroup never wait for one another.
+//   * s3 holds the same [2G][nt][4][64] checkpoints and [2G][edge][64] edges,
+//     indexed by (group, half) instead of (group, component): every store is
+//     a whole 512-B row.
+// flags are raised per stream (by either component's lane), so K3x and K4a
+// redo flagged streams as after k_lp_lane.
+template <int SPS, int FM>
+__global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf, PskParams p, Iir f) {
+  constexpr int TL = kLpT;
+  constexpr int CH = AMR_LP_CH;
+  constexpr int NCH = TL / CH, HC = CH / 2;
+  constexpr int R = NCH % 2 == 0 ? NCH / 2 : NCH;
+  static_assert(TL % CH == 0 && TL <= 64, "tile = whole chunks; one LO value of each component per lane");
+  static_assert(SPS > 0 && TL % SPS == 0 && FM < SPS, "static symbol slots");
+  __shared__ __attribute__((aligned(16))) double lo_lds[4][2][2][TL];   // [wave][tile parity][component][sample]
+  const int lane = threadIdx.x & 63;
+  const int hl = lane & 31, comp = lane >> 5;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t w = (int64_t)blockIdx.x * 2 + (wv >> 1);
+  const int64_t wc = w * 2 + (wv & 1);          // (group, stream half)
+  if (wc * 32 >= buf.n_streams) return;         // wave-uniform: no live stream in this half
+  const int64_t n = p.n, n2 = (n + 1) >> 1;
+  const int pad = p.pad2;
+  const int64_t nt = n / TL;
+  const int64_t s = wc * 32 + hl;
+  const bool live = s < buf.n_streams;
+  const int64_t G = (buf.n_streams + 63) / 64;
+  const int64_t ecap = lp_lane_edge_cap(pad);
+  // wave-uniform bases (SGPRs) + a small per-lane offset: one VGPR serves every row of a buffer
+  double* __restrict__ const ck = buf.s3 + (size_t)wc * nt * 4 * 64;                               // [..][lane]
+  double* __restrict__ const eh = buf.s3 + (size_t)2 * G * nt * 4 * 64 + (size_t)wc * ecap * 64;   // [..][lane]
+  double* __restrict__ const et = eh + (size_t)(pad + TL) * 64;
+  const double* __restrict__ const fl = buf.s2 + (size_t)wc * n2 * 64;                             // [..][hl * 2]
+  const unsigned fo = hl * 2;
+  const double* __restrict__ lov = buf.lo2 + (size_t)comp * n;                   // lo_c[i] of this lane's component
+  const double* __restrict__ lo4 = buf.lo + 2 * comp;                            // (mult, addend) at [4i]
+  auto F = [&](int64_t i) -> double { return (fl + ((i >> 1) * 64 + (i & 1)))[fo]; };
+  auto Xm = [&](int64_t i) { return F(i) * lov[i]; };
+  auto load_chunk = [&](int64_t t, int c, double2 (&r)[HC]) {
+    const double2* fp = reinterpret_cast<const double2*>(fl + (size_t)(t * (TL / 2) + c * HC) * 64);
+#pragma unroll
+    for (int k = 0; k < HC; ++k) r[k] = fp[k * 32 + hl];
+  };
+  // the tile's LO multipliers of both components: lanes < TL load one of each a tile ahead
+  auto load_lo = [&](int64_t t) -> double2 {
+    const double* lb = buf.lo2 + t * TL;
+    const unsigned i = lane < TL ? lane : 0;
+    return make_double2(lb[i], (lb + n)[i]);
+  };
+  auto put_lo = [&](int64_t t, double2 v) {
+    if (lane < TL) {
+      lo_lds[wv][t & 1][0][lane] = v.x;
+      lo_lds[wv][t & 1][1][lane] = v.y;
+    }
+  };
+  auto chunk_e = [&](int64_t t, int c, const double2 (&fv)[HC], double (&e)[CH]) {
+    const double2* lp = reinterpret_cast<const double2*>(&lo_lds[wv][t & 1][comp][c * CH]);
+#pragma unroll
+    for (int k = 0; k < HC; ++k) {
+      const double2 l = lp[k];
+      e[2 * k] = fv[k].x * l.x;
+      e[2 * k + 1] = fv[k].y * l.y;
+    }
+  };
+
+  // ---- forward pass (k_lp_lane's) ---------------------------------------------
+  double z[4];
+  float acc = __builtin_inff();
+  bool bad = false;
+  const double x0 = F(0) * lo4[0] + lo4[1];      // bb[0]: numpy's (f + 0j) * lo, +0 allowed (class-checked)
+  const double xl = Xm(n - 1);
+  bad |= __builtin_amdgcn_class(x0, kClsX);
+  const double e0 = 2.0 * x0 - Xm(pad);
+  bad |= __builtin_amdgcn_class(e0, kClsY);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) z[j] = f.zi[j] * e0;
+  for (int jj = 0; jj < pad; ++jj) {
+    const double e = 2.0 * x0 - Xm(pad - jj);
+    const double y = lp_step(z, f, e);
+    acc = tiny_min3(acc, e, y);
+    (eh + jj * 64)[lane] = y;
+  }
+  const int64_t nh = n < TL ? n : TL;           // tile 0 (holds bb[0]): edge buffer, not recomputed
+  for (int64_t i = 0; i < nh; ++i) {
+    const double e = i == 0 ? x0 : Xm(i);
+    const double y = lp_step(z, f, e);
+    acc = tiny_min3(acc, i == 0 ? y : e, y);
+    (eh + (pad + i) * 64)[lane] = y;
+  }
+  double2 ring[R][HC];
+  if (nt > 1) {
+#pragma unroll
+    for (int c = 0; c < R; ++c) load_chunk(1, c, ring[c]);
+    put_lo(1, load_lo(1));
+  }
+  for (int64_t t = 1; t < nt; ++t) {
+    const int64_t tn = t + 1 < nt ? t + 1 : t;
+    const double2 lon = load_lo(tn);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) (ck + (t * 4 + j) * 64)[lane] = z[j];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      double2 fv[HC];
+#pragma unroll
+      for (int k = 0; k < HC; ++k) fv[k] = ring[c % R][k];
+      if (c + R < NCH) load_chunk(t, c + R, ring[c % R]);
+      else load_chunk(tn, c + R - NCH, ring[c % R]);
+      double e[CH];
+      chunk_e(t, c, fv, e);
+#pragma unroll
+      for (int k = 0; k < CH; k += 2) {
+        const double y0 = lp_step(z, f, e[k]);
+        const double y1 = lp_step(z, f, e[k + 1]);
+        acc = tiny_min3(acc, e[k], e[k + 1]);
+        acc = tiny_min3(acc, y0, y1);
+      }
+    }
+    put_lo(tn, lon);
+  }
+  const int64_t i_tail = nt >= 1 ? nt * TL : nh;
+  int ne = 0;
+  for (int64_t i = i_tail; i < n; ++i) {
+    const double e = Xm(i);
+    const double y = lp_step(z, f, e);
+    acc = tiny_min3(acc, e, y);
+    (et + (ne++) * 64)[lane] = y;
+  }
+  double ylast = 0.0;
+  for (int jj = 0; jj < pad; ++jj) {
+    const double e = 2.0 * xl - Xm(n - 2 - jj);
+    ylast = lp_step(z, f, e);
+    acc = tiny_min3(acc, e, ylast);
+    (et + (ne++) * 64)[lane] = ylast;
+  }
+  bad |= !(acc >= kTinyHi);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(z[j]);
+  __threadfence();                              // checkpoints / edges re-read below
+
+  // ---- backward pass, slicing as it goes ----------------------------------------
+  const int64_t S = p.n_sym, first = p.first, sps = p.sps;
+  double pr = 0.0, pim = 0.0;                   // s[k+1]
+  uint32_t wacc = 0;
+  const bool qpsk = p.kind == kQpsk;
+  uint32_t* __restrict__ const wp = buf.words + (size_t)wc * 32 * p.n_words;   // [..][wo]: word j of this lane's stream
+  const unsigned wo = (unsigned)hl * (unsigned)p.n_words;
+  const bool wr = live && comp == 0;
+  // symbol sample k of this lane's component (k wave-uniform, descending from
+  // S - 1): both components to every lane, then diff_k = s[k+1] * conj(s[k])
+  // in numpy's fma form, exactly as K4a; words complete as k passes 16j (32j)
+  auto slice = [&](int64_t k, double y) {
+    if (k > S - 1) return;
+    const unsigned long long yb = __builtin_bit_cast(unsigned long long, y);
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)yb, (unsigned)yb, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(yb >> 32), (unsigned)(yb >> 32), false, false);
+    // [0]: lanes 0-31's value in both halves (re); [1]: lanes 32-63's (im)
+    const double sr = __builtin_bit_cast(double, ((unsigned long long)hi[0] << 32) | lo[0]);
+    const double si = __builtin_bit_cast(double, ((unsigned long long)hi[1] << 32) | lo[1]);
+    if (k <= S - 2) {
+      const double br = sr, bi = -si;
+      const double dr = __builtin_fma(pr, br, -(pim * bi));
+      if (qpsk) {
+        const double di = __builtin_fma(pr, bi, pim * br);
+        wacc |= qpsk_dibit(dr, di) << (30 - 2 * (int)(k & 15));
+        if ((k & 15) == 0) {
+          if (wr) (wp + (k >> 4))[wo] = wacc;
+          wacc = 0;
+        }
+      } else {
+        wacc |= (dr < 0 ? 1u : 0u) << (31 - (int)(k & 31));
+        if ((k & 31) == 0) {
+          if (wr) (wp + (k >> 5))[wo] = wacc;
+          wacc = 0;
+        }
+      }
+    }
+    pr = sr;
+    pim = si;
+  };
+  auto sym_out = [&](int64_t i, double y) {     // head / tail edges: a symbol sample at i?
+    if (i >= first && (i - first) % sps == 0) slice((i - first) / sps, y);
+  };
+  float accb = __builtin_inff();
+  double zb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) zb[j] = f.zi[j] * ylast;
+  for (int e = ne - 1; e >= 0; --e) {
+    const double y = lp_step(zb, f, (et + e * 64)[lane]);
+    accb = tiny_min3(accb, y, y);
+    const int64_t i = i_tail + e;
+    if (i < n) sym_out(i, y);
+  }
+  if (nt > 1) {
+    const int64_t q0 = first / SPS;
+    double cn[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cn[j] = (ck + ((nt - 1) * 4 + j) * 64)[lane];
+#pragma unroll
+    for (int c = 0; c < R; ++c) load_chunk(nt - 1, c, ring[c]);
+    put_lo(nt - 1, load_lo(nt - 1));
+    for (int64_t t = nt - 1; t >= 1; --t) {
+      double zf[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) zf[j] = cn[j];
+      const int64_t tp = t > 1 ? t - 1 : 1;     // the next (lower) tile's input and checkpoint in flight
+      double2 lop;
+      double yt[TL];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        double2 fv[HC];
+#pragma unroll
+        for (int k = 0; k < HC; ++k) fv[k] = ring[c % R][k];
+        if (c + R < NCH) load_chunk(t, c + R, ring[c % R]);
+        else load_chunk(tp, c + R - NCH, ring[c % R]);
+        double e[CH];
+        chunk_e(t, c, fv, e);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) yt[c * CH + k] = lp_step(zf, f, e[k]);
+      }
+      const int64_t kt = t * (TL / SPS) - q0;   // the tile's first symbol
+#pragma unroll
+      for (int k = TL - 1; k >= 1; k -= 2) {
+        const double y1 = lp_step(zb, f, yt[k]);
+        const double y0 = lp_step(zb, f, yt[k - 1]);
+        accb = tiny_min3(accb, y1, y0);
+        // the next tile's LO values and checkpoint: requested once the first outputs are
+        // consumed (their registers are free again: 230 VGPRs instead of 238 at sps 5), most
+        // of a backward tile before put_lo / the next re-run need them
+        if (k == TL - 7) lop = load_lo(tp);
+        if (k == TL - 11) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) cn[j] = (ck + (tp * 4 + j) * 64)[lane];
+        }
+        if (k % SPS == FM) slice(kt + (k - FM) / SPS, y1);
+        if ((k - 1) % SPS == FM) slice(kt + (k - 1 - FM) / SPS, y0);
+      }
+      put_lo(tp, lop);
+    }
+  }
+  for (int e = pad + (int)nh - 1; e >= 0; --e) {
+    const double y = lp_step(zb, f, (eh + e * 64)[lane]);
+    accb = tiny_min3(accb, y, y);
+    const int64_t i = e - pad;
+    if (i >= 0) sym_out(i, y);
+  }
+  bad |= !(accb >= kTinyHi);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(zb[j]);
+  if (bad && live) atomicOr(&buf.flags[s], 1);
+}
+
+// ---------------------------------------------------------------------------
 // low-pass, role-split: four waves per group of 64 streams -- (re, im) x
 // (forward / re-run, backward).  The forward waves run the forward pass
 // (checkpoints every TL2 samples, head / tail edges, the input/output zero
@@ -1209,19 +1489,29 @@ static int lp_split() {
   return v;
 }
 
+static int lp_half() {
+  // the fused low-pass with both components in one wave (k_lp_lane_h) in
+  // place of the two-wave fused k_lp_lane: AMR_LP_HALF=1 / 0 forces it on /
+  // off; on by default (static symbol slots, 4-wave workgroups, float64 f)
+  static const int v = [] { const char* e = getenv("AMR_LP_HALF"); return e ? (e[0] == '1' ? 1 : 0) : 1; }();
+  return v;
+}
+
+// which low-pass ran (AMR_LP_* of amr.h), returned by launch_lp
 template <int S_, int F_>
-static bool launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st) {
+static int launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st) {
   const int64_t g = (b.n_streams + 63) / 64;
   if (lp_split()) {
     hipLaunchKernelGGL((k_lp_lane2<S_, F_, kLpT2>), dim3((unsigned)g), dim3(256), 0, st, b, p, f);
-    return false;
+    return AMR_LP_LANE;
   }
   // the slicer inside the low-pass (static slots, both components in one
   // workgroup) once at least 32768 streams are live: it saves the symbols'
   // HBM round trip (+4-5 % per step at 16 x 4096 in flight) but lengthens a
-  // lone batch's low-pass (11.0 -> 13.7 ms: the re wave slices between
-  // barriers), which is what a small live set (a 1024-stream shard) waits
-  // on.  AMR_FUSED_SLICE=1 / 0 forces it on / off.
+  // lone batch's low-pass (11.0 -> 13.7 ms in the two-wave form, where the
+  // re wave slices between barriers; 12.7 ms in k_lp_lane_h: still above
+  // 11.0, so the threshold stays), which is what a small live set (a
+  // 1024-stream shard) waits on.  AMR_FUSED_SLICE=1 / 0 forces it on / off.
   static const int fuse_env = [] {
     const char* e = getenv("AMR_FUSED_SLICE");
     return e ? (e[0] == '1' ? 1 : 0) : -1;
@@ -1230,9 +1520,16 @@ static bool launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hip
   const bool fuse = S_ > 0 && lane_wpb() >= 2 && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
   if (b.f32f) {
     // the float32 hand-off needs the fused slicer (api.cpp asks psk_lane_fused first)
-    if (!(fuse && S_ != 0 && lane_wpb() == 4)) return false;
+    if (!(fuse && S_ != 0 && lane_wpb() == 4)) return AMR_LP_LANE;
     hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, S_ != 0>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
-    return true;
+    return AMR_LP_LANE_FUSED;
+  }
+  if constexpr (S_ != 0) {
+    // (k_lp_lane_h offsets a half's words by a 32-bit lane term: 32 * n_words must fit)
+    if (fuse && lane_wpb() == 4 && lp_half() && p.n_words < (1 << 26)) {
+      hipLaunchKernelGGL((k_lp_lane_h<S_, F_>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
+      return AMR_LP_LANE_HALF;
+    }
   }
   switch (lane_wpb()) {
     case 4:
@@ -1247,7 +1544,7 @@ static bool launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hip
       // a multiple of 16 blocks: the re/im XCD pairing is a bijection
       hipLaunchKernelGGL((k_lp_lane<S_, F_, 1>), dim3((unsigned)((2 * g + 15) / 16 * 16)), dim3(64), 0, st, b, p, f);
   }
-  return fuse;
+  return fuse ? AMR_LP_LANE_FUSED : AMR_LP_LANE;
 }
 
 // whether launch_psk_lowpass_lane will run the fused slicer for this batch
@@ -1265,12 +1562,12 @@ bool psk_lane_fused(const PskBuffers& b, const PskParams& p) {
 }
 
 hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st,
-                                   bool* sliced) {
+                                   bool* sliced, int* kernel) {
   if (f.nt != 5) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(b.flags, 0, (size_t)b.n_streams * 4, st);
   if (e != hipSuccess) return e;
   const int fm = (int)(p.first % (p.sps > 0 ? p.sps : 1));
-  bool fused = false;
+  int fused = AMR_LP_LANE;
   // the static symbol slots number tile t's symbols from t * (TL / SPS) - first / SPS:
   // valid (>= 0 from the first whole tile on) while first <= the tile length;
   // a later first (the C ABI allows any) takes the generic path
@@ -1282,7 +1579,8 @@ hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, cons
   else if (p.sps == 5 && fm == 0) fused = launch_lp<5, 0>(b, p, f, st);
   else if (p.sps == 20 && fm == 0) fused = launch_lp<20, 0>(b, p, f, st);
   else fused = launch_lp<0, 0>(b, p, f, st);
-  if (sliced) *sliced = fused;
+  if (sliced) *sliced = fused != AMR_LP_LANE;
+  if (kernel) *kernel = fused;
   return hipGetLastError();
 }
 

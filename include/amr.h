@@ -85,7 +85,8 @@ extern "C" {
                                   receiver (amr_hell_pixels, amr_hell_work_bytes, amr_hell_demod_host /
                                   _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL; the
                                   convolutional code (amr_conv_encoded_len, amr_conv_encode_host,
-                                  amr_viterbi_work_bytes, amr_viterbi_decode_host / _device) */
+                                  amr_viterbi_work_bytes, amr_viterbi_decode_host / _device);
+                                  amr_psk_plan_last_lowpass (AMR_LP_*) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -209,6 +210,16 @@ int amr_psk_split_design(const double *bp_b, const double *bp_a, int bp_ntaps, c
  * plan's last call used the hand-off (1) or float64 (0). */
 double amr_psk_f32_margin(const double *lp_b, const double *lp_a, int lp_ntaps);
 int amr_psk_plan_last_f32f(const amr_psk_plan *plan);
+/* Diagnostic (tests, A/B runs): which low-pass kernel the plan's last call ran
+ * in the lane layout -- AMR_LP_LANE: k_lp_lane or the
+ * role-split k_lp_lane2, symbols to HBM; AMR_LP_LANE_FUSED: k_lp_lane with the
+ * slicer fused, a component per wave; AMR_LP_LANE_HALF: k_lp_lane_h, both
+ * components in one wave, the slicer inline -- or -1 when that call ran no
+ * lane low-pass (another layout, or every stream through the exact path). */
+#define AMR_LP_LANE 0
+#define AMR_LP_LANE_FUSED 1
+#define AMR_LP_LANE_HALF 2
+int amr_psk_plan_last_lowpass(const amr_psk_plan *plan);
 /* Diagnostic (tests): the time-split passes alone over a host batch, chunk
  * outputs per lane (0: the plan's rule) -> the symbol samples
  * sym [n_streams][n_sym][re, im] (baseband[first::sps], modem.py:92, 209, as
