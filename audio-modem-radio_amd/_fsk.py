@@ -96,7 +96,9 @@ def fft_margin(n: int, baud, mark_freq, space_freq, samp_rate=96000):
     """F2's margin scale from a standard FFT rounding bound (host arithmetic
     in libamr.so, no device; include/amr.h amr_fsk_fft_margin): dict of tau,
     eps_fast, eps_ref, zmax (the bound on max_t ||z_t||_2 / peak|ext x|),
-    fast_blue, fast_M, ref_blue, ref_M."""
+    fast_blue, fast_M, ref_blue, ref_M.  Raises AmrError (AMR_E_INVALID) for
+    filters without a bound (responses that outlast the library's walk, or
+    grow); an FskPlan of them still decodes, every stream on the exact path."""
     _, ((mb, ma, mz), (sb, sa, sz)) = design_fsk(n, baud, mark_freq, space_freq, samp_rate)
     out = np.zeros(8)
     check(lib().amr_fsk_fft_margin(int(n), ptr(mb), ptr(ma), ptr(mz), ptr(sb), ptr(sa), ptr(sz), len(mb), ptr(out)))

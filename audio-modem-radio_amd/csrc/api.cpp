@@ -754,6 +754,9 @@ int amr_psk_split_bounds_host(amr_psk_plan* plan, const void* x, int dtype, int6
   if (dtype_size(dtype) == 0 || x_stride < plan->p.n) return fail(AMR_E_INVALID, "bad dtype / x_stride");
   if (!plan->split_designed) split_design(plan);
   if (!plan->split_ok || plan->p.n_sym < 2) return fail(AMR_E_INVALID, "no time-split layout for this plan");
+  // KS5 launches no strict kernel without decision bits: nothing to copy back
+  if (plan->p.n_bits < 1 || plan->p.n_words < 1)
+    return fail(AMR_E_INVALID, "amr_psk_split_bounds_host: this plan has no decision bits");
   const int64_t n = plan->p.n, es = dtype_size(dtype), S = plan->p.n_sym;
   int64_t have = plan->d_x_bytes;
   HIP_TRY(hipStreamSynchronize(plan->stream));
@@ -979,7 +982,9 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
   sp.z0tab = pl->split_tab ? pl->split_tab + (size_t)sp.w1 * 8 : nullptr;
   sp.zs = pl->split_zs;
   pl->split_L = sp.L;
-  if (pl->strict_ok && split_strict_on(pl) && sp.conv) {
+  // (a diagnostic's explicit chunk runs as given, without the strict
+  // bookkeeping; fsk_api.cpp fsk_split_params likewise rounds only its own chunk)
+  if (L <= 0 && pl->strict_ok && split_strict_on(pl) && sp.conv) {
     const StrictDesign& d = pl->sdes;
     // chunks on block boundaries (the per-block step bounds stay within a lane)
     sp.L = (sp.L + kStrictBlk - 1) / kStrictBlk * kStrictBlk;

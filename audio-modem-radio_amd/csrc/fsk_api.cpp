@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -395,6 +396,7 @@ struct amr_fsk_plan {
   int n_slots = 0;
   bool ran_exact = false;      // the last call ran the exact path (its count is in xlist[max_streams])
   int exact_mode = 1;          // amr_fsk_plan_set_exact_mode: 0 off, 1 F2's flags, 2 every stream
+  bool no_bound = false;       // fsk_fft_bound found no tau (p.tau = +inf): mode 1 runs as mode 2
   int64_t scratch_bytes = 0;
   // the time-split F1 (fsk_kernels.hip FS1-FS3): designed
   // with the plan; used for calls of at most kFskSplitMaxStreams streams
@@ -653,7 +655,7 @@ bool use_split(const amr_fsk_plan* pl, int64_t B) {
 int run_fsk_f1(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, bool exact) {
   FskParams p = pl->p;
   if (!(exact && pl->exact_on && pl->exact_mode != 0)) p.amb = nullptr;
-  p.force_exact = pl->exact_mode == 2 ? 1 : 0;
+  p.force_exact = pl->exact_mode == 2 || pl->no_bound ? 1 : 0;
   if (pl->split_now) {
     if (int rc = ensure_split_buffers(pl, B)) return rc;
     if (fsk_split_strict_on(pl))
@@ -1057,11 +1059,9 @@ bool fsk_geometry(int64_t n, int64_t sps, int nt, int64_t max_streams, FskGeom& 
 // ||ifft(h)||_1 * peak|ext x|, the margin F2 adds for split calls.  Refused
 // when a warm-up exceeds n / 4 or the margin would pass 2^-24 of the peak.
 constexpr double kFskSplitSafety = 64.0;
-bool fsk_split_design(const FskIir& f, int nt, int64_t n, int64_t* w_out, double* kappa_out, double* hl1_out) {
-  if (nt != 7 || n < 64) return false;
-  const double u = 0x1p-53;
-  IirGains g[2];
-  double G = 0.0;
+// both tones' response sums (iir_design.h iir_gains): walked once, shared by
+// the split design and F2's FFT bound
+void fsk_tone_gains(const FskIir& f, int nt, IirGains g[2]) {
   for (int t = 0; t < 2; ++t) {
     Iir fi{};
     fi.nt = nt;
@@ -1070,9 +1070,14 @@ bool fsk_split_design(const FskIir& f, int nt, int64_t n, int64_t* w_out, double
       fi.a[i] = f.a[t][i];
     }
     g[t] = iir_gains(fi);
-    if (!g[t].ok) return false;
-    G = std::max(G, g[t].g1 * (1.0 + g[t].h1));
+    if (!g[t].ok) return;        // no design and no bound without both
   }
+}
+bool fsk_split_design(const IirGains g[2], int nt, int64_t n, int64_t* w_out, double* kappa_out, double* hl1_out) {
+  if (nt != 7 || n < 64 || !g[0].ok || !g[1].ok) return false;
+  const double u = 0x1p-53;
+  double G = 0.0;
+  for (int t = 0; t < 2; ++t) G = std::max(G, g[t].g1 * (1.0 + g[t].h1));
   const double tol = 0x1p-4 * u * G;
   int64_t w = 0;
   for (int t = 0; t < 2; ++t) {
@@ -1129,7 +1134,8 @@ int64_t lpf_of(int64_t n) {
     }
   return n > 1 ? std::max(r, n) : r;
 }
-bool fsk_fft_bound(const FskIir& f, int nt, int64_t n, int pad, FskFftBound& o) {
+bool fsk_fft_bound(const FskIir& f, const IirGains gains[2], int nt, int64_t n, int pad, FskFftBound& o) {
+  if (!gains[0].ok || !gains[1].ok) return false;
   const double u = 0x1p-53;
   auto gam = [&](double k) { return k * u / (1.0 - k * u); };
   auto eta_of = [&](int64_t p) {
@@ -1167,9 +1173,9 @@ bool fsk_fft_bound(const FskIir& f, int nt, int64_t n, int pad, FskFftBound& o) 
       fi.a[i] = f.a[t][i];
     }
     for (int i = 0; i < nt - 1; ++i) fi.zi[i] = f.zi[t][i];
-    const IirGains g = iir_gains(fi);
+    const IirGains& g = gains[t];
     const double R = zi_response_l2(fi);
-    if (!g.ok || !(R >= 0.0)) return false;
+    if (!(R >= 0.0)) return false;
     const double G = g.h1 * (1.0 + 0x1p-20);
     zb = std::max(zb, G * G * std::sqrt(m1) + 2.0 * G * R + R * R);
   }
@@ -1199,7 +1205,9 @@ int amr_fsk_fft_margin(int64_t n, const double* mb, const double* ma, const doub
     f.zi[1][i] = szi[i];
   }
   FskFftBound o;
-  if (!fsk_fft_bound(f, nt, n, 3 * nt, o)) return fail(AMR_E_INVALID, "amr_fsk_fft_margin: no bound for these filters at n");
+  IirGains g[2];
+  fsk_tone_gains(f, nt, g);
+  if (!fsk_fft_bound(f, g, nt, n, 3 * nt, o)) return fail(AMR_E_INVALID, "amr_fsk_fft_margin: no bound for these filters at n");
   out[0] = o.tau;
   out[1] = o.eps_fast;
   out[2] = o.eps_ref;
@@ -1231,7 +1239,9 @@ int amr_fsk_split_design(int64_t n, const double* mb, const double* ma, const do
   }
   int64_t w = 0;
   double k = 0.0, h = 0.0;
-  if (!fsk_split_design(f, nt, n, &w, &k, &h)) return fail(AMR_E_INVALID, "no time-split design for these filters at n");
+  IirGains g[2];
+  if (n >= 64) fsk_tone_gains(f, nt, g);
+  if (!fsk_split_design(g, nt, n, &w, &k, &h)) return fail(AMR_E_INVALID, "no time-split design for these filters at n");
   if (warmup) *warmup = w;
   if (kappa) *kappa = k;
   if (hilbert_l1_out) *hilbert_l1_out = h;
@@ -1379,13 +1389,20 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
   }
   {
     FskFftBound fb;
-    if (!fsk_fft_bound(pl->f, nt, n, p.pad, fb)) {
-      fsk_plan_free(pl);
-      return fail(AMR_E_INVALID, "no FFT rounding bound for these filters at length " + std::to_string(n));
+    IirGains g[2];
+    fsk_tone_gains(pl->f, nt, g);
+    if (fsk_fft_bound(pl->f, g, nt, n, p.pad, fb)) {
+      p.tau = fb.tau;
+    } else {
+      // no bound (a band-pass whose responses outlast iir_design.h's walk, or
+      // grow): no compare of F2's can be kept, so every stream of every call
+      // goes through the exact path (run_fsk_f1 force_exact) -- the
+      // reference decodes these captures, and so does the plan
+      pl->no_bound = true;
+      p.tau = std::numeric_limits<double>::infinity();
     }
-    p.tau = fb.tau;
     double kappa = 0.0, hl1 = 0.0;
-    pl->split_ok = fsk_split_design(pl->f, nt, n, &pl->split_w, &kappa, &hl1);
+    pl->split_ok = fsk_split_design(g, nt, n, &pl->split_w, &kappa, &hl1);
     pl->split_kappa = kappa;
     pl->split_hl1 = hl1;
     pl->split_tau = p.tau + kappa * hl1;
@@ -1513,6 +1530,7 @@ int amr_fsk_split_bounds_host(amr_fsk_plan* plan, const void* x, int dtype, int6
   std::lock_guard<std::mutex> lk(plan->mu);
   HIP_TRY(hipSetDevice(plan->device));
   if (!plan->split_ok || !fsk_split_conv_on(plan)) return fail(AMR_E_INVALID, "no convolution-start split F1 for this plan");
+  if (plan->p.n_bits == 0) return fail(AMR_E_INVALID, "amr_fsk_split_bounds_host: this plan has no decision bits");
   if (B > plan->max_streams || B > 65535) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
   if (x_stride < plan->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
   const int saved = plan->strict_mode;

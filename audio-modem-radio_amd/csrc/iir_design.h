@@ -42,6 +42,7 @@ inline IirGains iir_gains(const Iir& f) {
       for (int j = 0; j < N; ++j) live = std::max(live, std::fabs(z[j]));
     }
     r.g1 += t;
+    if (!std::isfinite(r.g1)) return r;          // a growing response: no gains
     r.tail.push_back(t);
     decayed = live < 1e-40 && m > 4 * N;
   }
@@ -80,6 +81,7 @@ inline double zi_response_l2(const Iir& f) {
     for (int j = 0; j < N - 1; ++j) z[j] = z[j + 1] - (long double)f.a[j + 1] * y;
     z[N - 1] = -(long double)f.a[N] * y;
     s2 += y * y;
+    if (!std::isfinite(s2)) return -1.0;
     long double live = 0.0L;
     for (int j = 0; j < N; ++j) live = std::max(live, std::fabs(z[j]));
     if (live < 1e-40L && m > 4 * N) return (double)std::sqrt(s2) * (1.0 + 0x1p-30);

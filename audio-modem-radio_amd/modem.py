@@ -121,14 +121,18 @@ def bpsk_demodulate_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_r
 
 
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
-    """Ragged batch: streams of different lengths, grouped by length on the host."""
+    """Ragged batch: streams of different lengths and dtypes, grouped by
+    (length, dtype) on the host -- each result == <kind>_demodulate(stream):
+    a stream keeps its own dtype (and with it its odd extension, _as_batch)
+    rather than the one numpy would promote a mixed stack to."""
     fn = {"qpsk": qpsk_demodulate_batch, "bpsk": bpsk_demodulate_batch}[kind]
-    by_len: dict = {}
-    for i, s in enumerate(streams):
-        by_len.setdefault(len(s), []).append(i)
+    rows = [_as_batch(s) for s in streams]
+    groups: dict = {}
+    for i, r in enumerate(rows):
+        groups.setdefault((len(r), r.dtype), []).append(i)
     out = [b""] * len(streams)
-    for n, idx in by_len.items():
-        res = fn(np.stack([_as_batch(streams[i]) for i in idx]), baud, carrier, samp_rate)
+    for idx in groups.values():
+        res = fn(np.stack([rows[i] for i in idx]), baud, carrier, samp_rate)
         for i, r in zip(idx, res):
             out[i] = r
     return out

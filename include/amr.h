@@ -264,7 +264,10 @@ int amr_psk_plan_last_strict(const amr_psk_plan *plan);
  * each symbol component's |split - reference| and, per stream, scalars
  * [n_streams][4]: E1 (band-pass forward), F (band-pass output), X (mixer
  * output) and P3 (low-pass input peak; negative when the a-posteriori caps
- * failed and the stream would be flagged). */
+ * failed and the stream would be flagged).  A plan without decision bits
+ * (fewer than two symbol centres) is refused, AMR_E_INVALID, and nothing is
+ * written.  (amr_psk_split_symbols_host with an explicit chunk runs that
+ * chunk as given, without the strict bookkeeping, whatever the plan's mode.) */
 int amr_psk_split_bounds_host(amr_psk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
                               double *sym, double *ebound, double *scalars);
 /* The strict design from the filters alone (host arithmetic; the tests'
@@ -442,7 +445,11 @@ int amr_fsk_plan_split_info(amr_fsk_plan *plan, int *last_split, int64_t *warmup
  * fast path's and pocketfft's relative 2-norm transform errors eps_fast /
  * eps_ref, the bound on max ||z||_2 / peak|ext x| over both tones, whether
  * the fast path runs Bluestein and its length, whether pocketfft does and its
- * length.  The filters as amr_fsk_plan_create takes them. */
+ * length.  The filters as amr_fsk_plan_create takes them.  AMR_E_INVALID
+ * when there is no bound: a band-pass whose responses have not decayed within
+ * the 4 000 000 steps walked, or grow.  A plan of such filters is still
+ * created (amr_fsk_plan_margin then reports tau = +inf) and sends every
+ * stream through the exact path, as exact mode 2 does. */
 int amr_fsk_fft_margin(int64_t n_samples, const double *mark_b, const double *mark_a, const double *mark_zi,
                        const double *space_b, const double *space_a, const double *space_zi, int ntaps, double *out);
 /* a plan's F2 margin scales: tau (serial F1) and tau_split (time-split F1:
@@ -472,7 +479,8 @@ int amr_fsk_split_strict_design(const double *b, const double *a, const double *
 /* Diagnostic (tests): the strict split F1 over a host batch: z_out
  * [n_streams][n_samples][2] (mark, space), bnd_out [n_streams][2][8] the
  * per-tone maxima as doubles (D1max, E1max, max|y1|, D2max, S1max, -, F, -),
- * peak_out [n_streams] max |ext x|.  Synchronous. */
+ * peak_out [n_streams] max |ext x|.  Synchronous.  A plan without decision
+ * bits is refused (AMR_E_INVALID), nothing written. */
 int amr_fsk_split_bounds_host(amr_fsk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
                               double *z_out, double *bnd_out, double *peak_out);
 /* the split F1's band-pass output itself (a diagnostic the tests compare with

@@ -135,3 +135,26 @@ def test_pocketfft_error_within_its_share(n, baud, mark, space, built_lib):
             assert err <= share, (err, share)
             worst_ratio = min(worst_ratio, share / max(err, 1e-300))
     print(f"n={n}: pocketfft's envelope error <= its bound share / {worst_ratio:.0f}")
+
+
+def _no_bound_cases():
+    """The fixture's parameter sets whose band-pass responses have not decayed
+    below 1e-40 within the 4 000 000 steps iir_gains / zi_response_l2 walk
+    (csrc/iir_design.h): the slow class, the unstable designs, and a band edge
+    1e-6 of Nyquist from 0 or 1."""
+    import fsk_edge_cases as ec
+    out = [c for c in ec.CASES if c["edge"] in ("slow", "unstable")]
+    out += [c for c in ec.CASES if c["id"] in ("e12_edge0", "e15_edge0", "e16_edge0", "e18_edgenyq", "e21_edgenyq")]
+    return out
+
+
+@pytest.mark.parametrize("case", _no_bound_cases(), ids=lambda c: c["id"])
+def test_no_bound_for_undecayed_responses(case, built_lib):
+    """amr_fsk_fft_margin keeps refusing these (AMR_E_INVALID): there is no
+    finite tau to report.  A plan of the same filters is still created -- with
+    every stream on the exact path (tests/test_gpu_fsk_edge.py)."""
+    import _amr
+    import _fsk
+    with pytest.raises(_amr.AmrError) as e:
+        _fsk.fft_margin(1000, case["baud"], case["f0"], case["f1"], case["samp_rate"])
+    assert e.value.code == _amr.AMR_E_INVALID and "no bound" in str(e.value)

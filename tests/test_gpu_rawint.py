@@ -156,3 +156,47 @@ def test_raw_fsk_batches(dt):
         want = [oracle.fsk_demodulate(r, 9600, 12000.0, 24000.0, raw_int16=True) for r in x]
         bad += [(B, layout, i) for i in range(B) if got[i] != want[i]]
     assert not bad, bad
+
+
+@pytest.mark.parametrize("kind", ["qpsk", "bpsk"])
+def test_ragged_streams_keep_their_dtypes(kind):
+    """demodulate_ragged with same-length streams of uint8, int8, int16,
+    float32 and float64, interleaved with a second length: each result is
+    <kind>_demodulate(row) and the oracle's bytes for the row in its OWN
+    dtype.  The rows are unframed symbols (no sync: the bytes start at the
+    first bit) with full-scale end samples, so every integer row's odd
+    extension wraps in its dtype and the wrap decides its first bytes --
+    asserted against the oracle on the row's float64 copy -- which stacking
+    the row with another dtype (numpy promotes) would lose."""
+    import modem
+    import synth
+    from oracle import oracle
+    rng = np.random.default_rng(77)
+    baud, n, n2 = 9600, 3000, 2345
+    wave = synth.qpsk_waveform if kind == "qpsk" else synth.bpsk_waveform
+    single = modem.qpsk_demodulate if kind == "qpsk" else modem.bpsk_demodulate
+    ofn = oracle.qpsk_demodulate if kind == "qpsk" else oracle.bpsk_demodulate
+
+    def row(dt, m):
+        w = wave(rng.integers(0, 256, 400, dtype=np.uint8).tobytes(), baud, 3000.0, 96000.0)[1234:]
+        x = np.clip(0.6 * w[:m] + rng.normal(0, 0.05, m), -1, 1)
+        x[0], x[-1] = 0.99, -0.99                         # wrapping edges in every integer dtype
+        if np.dtype(dt).kind == "f":
+            return x.astype(dt)
+        if dt == np.uint8:
+            return np.clip(np.round(128 + 127 * x), 0, 255).astype(np.uint8)
+        return np.round(x * np.iinfo(dt).max).astype(dt)
+
+    streams = []
+    for dt in (np.uint8, np.int8, np.int16, np.float32, np.float64):
+        streams += [row(dt, n), row(dt, n2)]
+    want = [ofn(s, baud=baud, raw_int16=True) for s in streams]
+    for s, w in zip(streams, want):
+        if s.dtype.kind in "iu":
+            assert w != ofn(s.astype(np.float64), baud=baud), (str(s.dtype), s.size)
+    got = modem.demodulate_ragged(kind, streams, baud)
+    bad = []
+    for i, (s, g, w) in enumerate(zip(streams, got, want)):
+        if g != w or g != single(s, baud=baud):
+            bad.append((i, str(s.dtype), s.size))
+    assert not bad, bad

@@ -294,3 +294,66 @@ def test_one_capture_drop_in_latency():
         tr.append(time.perf_counter() - t)
     print(f"one capture: split {np.median(ts) * 1e3:.3f} ms (min {min(ts) * 1e3:.3f}), "
           f"row {np.median(tr) * 1e3:.3f} ms")
+
+
+def test_explicit_chunk_after_a_strict_call():
+    """An explicit chunk is the chunk that runs, whatever the plan ran before:
+    split_bounds(x) designs the strict mode (whose own chunks sit on 16-sample
+    block boundaries), then split_symbols(x, 130) on the same plan reports
+    chunk 130 and gives the restatement's symbols at L = 130 -- the symbols
+    of the same call on a fresh plan."""
+    import _amr
+    from oracle import oracle
+    kind, baud, fc, fs, n, B = "qpsk", 9600, 3000.0, 96000, 24000, 2
+    x = _batch(kind, B, n, baud, fc, fs, 5, 0.2)
+    pl = _amr.PskPlan(kind, n, baud, fc, fs, max_streams=B)
+    pl.split_bounds(x)
+    assert pl.split_info()["chunk"] % 16 == 0
+    got = pl.split_symbols(x, 130)
+    info = pl.split_info()
+    assert info["chunk"] == 130, info
+    tables = _amr.split_state_tables(kind, n, baud, fc, fs)
+    fresh = _amr.PskPlan(kind, n, baud, fc, fs, max_streams=B).split_symbols(x, 130)
+    for i in range(B):
+        want = oracle.psk_split_symbols(kind, x[i], baud, fc, fs, 130, info["warmup_bp"], info["warmup_lp"],
+                                        tables=tables)
+        assert np.array_equal(got[i], want), (i, np.abs(got[i] - want).max())
+        assert np.array_equal(got[i], fresh[i]), i
+    # the same with the strict mode on for the plan's own calls (the state in
+    # which split_params used to round an explicit 130 up to 144)
+    pl.set_split_strict(True)
+    pl.set_layout("split")
+    out, _ = pl.demod_host(x)
+    assert pl.last_strict() and pl.split_info()["chunk"] % 16 == 0
+    assert list(out) == list(oracle.psk_demod_batch(kind, x, baud, fc, fs)[0])
+    again = pl.split_symbols(x, 130)
+    assert pl.split_info()["chunk"] == 130, pl.split_info()
+    assert np.array_equal(again, got)
+    # and a strict call after it still runs on block boundaries
+    pl.split_bounds(x)
+    assert pl.split_info()["chunk"] % 16 == 0
+
+
+def test_fsk_explicit_chunk_after_a_strict_call():
+    """The same sequence on the FSK split F1 (fsk_split_params rounds only the
+    plan's own chunk): split_bounds(x), then split_bandpass(x, 130) runs at
+    130 and equals the restatement and a fresh plan's output."""
+    import _amr
+    import _fsk
+    import synth
+    from oracle import oracle
+    n, baud, mark, space, B = 24000, 9600, 12000.0, 24000.0, 2
+    x = synth.fsk_batch(B, n, baud, mark, space, seed=9, distinct=B, noise=0.2)
+    pl = _fsk.FskPlan(n, baud, mark, space, max_streams=B)
+    pl.split_bounds(x)
+    assert pl.split_info()["chunk"] % 16 == 0
+    got = pl.split_bandpass(x, 130)
+    info = pl.split_info()
+    assert info["chunk"] == 130, info
+    fresh = _fsk.FskPlan(n, baud, mark, space, max_streams=B).split_bandpass(x, 130)
+    _, tones = _fsk.design_fsk(n, baud, mark, space, 96000)
+    for i in range(B):
+        for t, (b, a, zi) in enumerate(tones):
+            want = oracle.split_filtfilt(b, a, x[i], 130, info["warmup"], tables=_amr.state_tables(b, a, zi, info["warmup"]))
+            assert np.array_equal(got[i, :, t], want), (i, t)
+        assert np.array_equal(got[i], fresh[i]), i

@@ -129,3 +129,52 @@ print("BAD", bad, "STRICT", all(strict), len(strict))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("BAD")][-1]
     assert line.startswith("BAD [] STRICT True"), line
+
+
+SENTINEL = -7.25
+
+
+def _untouched(*arrays):
+    return all(np.all(a == SENTINEL) for a in arrays)
+
+
+def test_bounds_refused_without_decision_bits():
+    """amr_psk_split_bounds_host on a plan with no decision bits (300 Bd and
+    less than two symbol centres in the capture, so n_bits == 0) returns
+    AMR_E_INVALID and
+    writes nothing.  KS5 (launch_psk_split_slice) launches no strict kernel for
+    such a plan, so a copy of the strict scratch would be uninitialised
+    memory.  No plan with n_bits == 0 can pass the entry's own n_sym >= 2
+    check (n_bits = (n_sym - 1) * bits per symbol), so the refusal asserted
+    here is the one that happens: the outputs keep their sentinel."""
+    import _amr
+    from _amr import lib, ptr
+    for kind, n in (("qpsk", 200), ("bpsk", 400), ("bpsk", 200), ("qpsk", 161)):
+        pl = _amr.PskPlan(kind, n, 300, 3000.0, 96000, max_streams=2)
+        S = max(0, (pl.n - pl.first + pl.sps - 1) // pl.sps)
+        assert S == (0 if (kind, n) == ("bpsk", 200) else 1)
+        x = np.random.default_rng(n).normal(0, 0.3, (2, n)).astype(np.float32)
+        assert pl.demod_host(x)[0] == [b"", b""]
+        sym, eb, sc = (np.full(s, SENTINEL) for s in ((2, max(S, 1), 2), (2, max(S, 1)), (2, 4)))
+        rc = lib().amr_psk_split_bounds_host(pl.handle, ptr(x), _amr.DTYPES[x.dtype], 2, n, ptr(sym), ptr(eb), ptr(sc))
+        assert rc == _amr.AMR_E_INVALID, (kind, n, rc)
+        assert _untouched(sym, eb, sc), (kind, n)
+
+
+def test_fsk_bounds_refused_without_decision_bits():
+    """The mirror for amr_fsk_split_bounds_host: 300 Bd at 96 kHz with 150
+    samples (less than half a bit: n_bits == 0).  Such a plan has no split
+    design either (the band-pass's warm-up exceeds n / 4 whenever n is below
+    one bit), so it is refused before any launch; z, the maxima and the peaks
+    keep their sentinel."""
+    import _amr
+    import _fsk
+    from _amr import lib, ptr
+    n = 150
+    pl = _fsk.FskPlan(n, 300, 1200.0, 2200.0, 96000, max_streams=2)
+    x = np.random.default_rng(n).normal(0, 0.3, (2, n)).astype(np.float32)
+    assert pl.demod_host(x)[0] == [b"", b""]
+    z, bnd, pk = (np.full(s, SENTINEL) for s in ((2, n, 2), (2, 2, 8), (2,)))
+    rc = lib().amr_fsk_split_bounds_host(pl.handle, ptr(x), _amr.DTYPES[x.dtype], 2, n, ptr(z), ptr(bnd), ptr(pk))
+    assert rc == _amr.AMR_E_INVALID, rc
+    assert _untouched(z, bnd, pk)

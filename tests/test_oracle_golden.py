@@ -282,3 +282,28 @@ def test_oracle_wav_pipeline_matches_reference(wav_golden):
             frames = decoder.parse_fbp_stream_enhanced(raw)
         got = [{"name": f["name"], "data": compression.intelligent_decompress(f["data"]).hex()} for f in frames]
         assert got == case["files"], case["id"]
+
+
+def _fsk_edge_cases():
+    import fsk_edge_cases as ec
+    return ec.load()[0]["cases"]
+
+
+@pytest.mark.parametrize("case", _fsk_edge_cases(), ids=lambda c: c["id"])
+def test_oracle_matches_reference_fsk_edges(case):
+    """The oracle against the reference's own fsk_demodulate at the edges of
+    its parameter space (tests/golden/make_fsk_edge_golden.py): narrow
+    band-passes at low and non-integer baud, a band edge 1e-6 from 0 or
+    Nyquist (and on it: the same ValueError), equal / overlapping / swapped
+    tone bands, band-passes whose responses outlast the library's bound walk,
+    and designs whose transfer-function form is unstable (inf / NaN
+    envelopes).  Each input is regenerated from its seed and must have the
+    recorded SHA-256; int16 captures go in raw, as the reference got them."""
+    import warnings
+
+    import fsk_edge_cases as ec
+    x = ec.case_input(case, ec.load()[1])
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        got = ec.outcome(lambda: ec.demod(oracle, case, x, raw_int16=True))
+    assert got == expected(case), (case["id"], case["params"])
