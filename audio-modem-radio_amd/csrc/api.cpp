@@ -15,6 +15,7 @@
 
 #include "amr_internal.h"
 #include "api_common.h"
+#include "dev_mem.h"
 #include "iir_design.h"
 #include "split_strict.h"
 
@@ -144,11 +145,11 @@ int device_crc(int dev, const uint32_t** table, const uint32_t** x2n) {
   if (dev < 0 || dev >= 64) return fail(AMR_E_INVALID, "device ordinal out of range");
   if (!g_crc[dev].d) {
     static const CrcTables t;
-    uint32_t* p = nullptr;
-    HIP_TRY(hipMalloc(&p, sizeof(uint32_t) * 288));
-    HIP_TRY(hipMemcpy(p, t.table, sizeof(t.table), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p + 256, t.x2n, sizeof(t.x2n), hipMemcpyHostToDevice));
-    g_crc[dev].d = p;
+    DevBuf p;                                   // freed if an upload fails; kept for the process once filled
+    HIP_TRY(p.reserve(sizeof(uint32_t) * 288, nullptr));
+    HIP_TRY(hipMemcpy(p.get(), t.table, sizeof(t.table), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p.as<uint32_t>() + 256, t.x2n, sizeof(t.x2n), hipMemcpyHostToDevice));
+    g_crc[dev].d = static_cast<uint32_t*>(p.detach());
   }
   *table = g_crc[dev].d;
   *x2n = g_crc[dev].d + 256;
@@ -165,30 +166,25 @@ static bool same_bits(double a, double b) {
 
 // Per-device staging of the synchronous host entries that take no plan
 // (amr_fec_decode_host, amr_frame_parse_host): grow-only buffers kept for the
-// process instead of hipMalloc/hipFree on every call; one call per device at a
-// time (the lock is held for the whole call).
+// process instead of an allocation and a free on every call; one call per device at a
+// time (the lock is held for the whole call).  Never destroyed: the blocks
+// live as long as the process, and nothing frees device memory at exit.
 struct HostStaging {
   std::mutex mu;
-  void* buf[6] = {};
-  int64_t bytes[6] = {};
+  DevBuf buf[6];
 };
-HostStaging g_staging[64];
+HostStaging& host_staging(int dev) {
+  static HostStaging* const all = new HostStaging[64];
+  return all[dev];
+}
 
+// slot `slot` at least `need` bytes (exactly `need`, or 256 for a smaller
+// request); the entries are synchronous and run on the null stream, so no
+// queued work reads the block a grow replaces
 hipError_t staging_get(HostStaging& hs, int slot, int64_t need, void** out) {
-  if (hs.bytes[slot] < need || !hs.buf[slot]) {
-    if (hs.buf[slot]) {
-      hipError_t e = hipFree(hs.buf[slot]);
-      if (e != hipSuccess) return e;
-    }
-    hs.buf[slot] = nullptr;
-    hs.bytes[slot] = 0;
-    const int64_t grow = std::max<int64_t>(need, hs.bytes[slot] * 2);
-    hipError_t e = hipMalloc(&hs.buf[slot], (size_t)std::max<int64_t>(grow, 256));
-    if (e != hipSuccess) return e;
-    hs.bytes[slot] = std::max<int64_t>(grow, 256);
-  }
-  *out = hs.buf[slot];
-  return hipSuccess;
+  const hipError_t e = hs.buf[slot].reserve(std::max<int64_t>(need, 256), nullptr);
+  *out = hs.buf[slot].get();
+  return e;
 }
 
 }  // namespace
@@ -225,29 +221,26 @@ struct amr_psk_plan {
   int64_t max_streams = 0, groups = 0;
   int64_t m1_pairs = 0, m2_pairs = 0;
   int64_t out_cap = 0;
-  // HBM scratch
-  double* lo = nullptr;
-  double* lo2 = nullptr;
+  // Every device buffer the plan owns (dev_mem.h DevBuf); plan_free releases
+  // them together, after the stream is drained and before it is destroyed.
+  struct Mem {
+    // HBM scratch, allocated with the plan: what amr_psk_plan_scratch_bytes counts (psk_scratch_bytes)
+    DevBuf lo, lo2;
+    DevBuf s1_base, s3_base;   // the row layout grows them on first use (grow_scratch)
+    DevBuf s2, words, flags;
+    DevBuf split_peak;         // [max_streams], then flags [max_streams] and the count
+    // time-split layout, on first use
+    DevBuf split_tab;          // [w1][8] K, then [w1 + 1][8] Z0 (split_state_tables), with the design
+    DevBuf split_zs;           // [B][c1][8] chunk start states (grown per launch)
+    DevBuf strict_tab, strict_bnd;
+    DevBuf strict_sc;          // the per-stream scratch of the block bound (PskSplit::sc), grown per call
+    // staging for the host API (lazily sized)
+    DevBuf d_x;
+    DevBuf d_out, d_len, d_sync;   // one group: all three or none (reserve_all)
+    DevBuf d_edge;             // amr_psk_demod_host_edges' table [max_streams][2 pad1]
+  } mem;
   double* s1 = nullptr;   // = s1_base + kFrontSlack (backward prefetch may read below)
-  double* s2 = nullptr;
   double* s3 = nullptr;   // = s3_base + kFrontSlack
-  double* s1_base = nullptr;
-  double* s3_base = nullptr;
-  int64_t s1_bytes = 0, s3_bytes = 0;   // allocated (the row layout grows them on first use)
-  uint32_t* words = nullptr;
-  int32_t* flags = nullptr;
-  int64_t scratch_bytes = 0;
-  // staging for the host API (lazily sized)
-  void* d_x = nullptr;
-  int64_t d_x_bytes = 0;
-  uint8_t* d_out = nullptr;
-  int64_t* d_len = nullptr;
-  int64_t* d_sync = nullptr;
-  double* d_edge = nullptr;   // amr_psk_demod_host_edges' table [max_streams][2 pad1]
-  int64_t d_edge_bytes = 0;
-  uint8_t* d_fec = nullptr;   // FEC host API staging
-  int64_t* d_fec_len = nullptr;
-  int32_t* d_crc = nullptr;
   // timing
   bool timing = false;
   int inflight = 1;             // amr_psk_plan_set_inflight hint
@@ -261,12 +254,8 @@ struct amr_psk_plan {
   bool split_designed = false, split_ok = false;
   int64_t split_w1 = 0, split_w2 = 0, split_L = 0;
   double split_kappa = 0.0;
-  unsigned long long* split_peak = nullptr;   // [max_streams], then flags [max_streams] and the count
-  int32_t* split_flag = nullptr;
+  int32_t* split_flag = nullptr;    // views into mem.split_peak
   int32_t* split_count = nullptr;
-  double* split_tab = nullptr;    // [w1][8] K, then [w1 + 1][8] Z0 (split_state_tables), with the design
-  double* split_zs = nullptr;     // [B][c1][8] chunk start states (grown per launch)
-  int64_t split_zs_bytes = 0;
   // the split layout's STRICT bound (split_strict.h): -1 = the process default
   // (AMR_PSK_SPLIT_STRICT=1), else amr_psk_plan_set_split_strict; designed on
   // the first strict call (the device tables, split_strict.h strict_bp_append |
@@ -275,10 +264,6 @@ struct amr_psk_plan {
   int strict_mode = -1;
   bool strict_designed = false, strict_ok = false;
   StrictDesign sdes;
-  double* strict_tab = nullptr;
-  unsigned long long* strict_bnd = nullptr;
-  double* strict_sc = nullptr;    // the per-stream scratch of the block bound (PskSplit::sc), grown per call
-  int64_t strict_sc_bytes = 0;
   bool last_f32f = false;       // the last lane-layout call handed f over in float32
   int last_lowpass = -1;        // AMR_LP_* of the last lane-layout call's low-pass (-1: none ran)
   bool last_strict = false;     // the last split call decided with the strict bound
@@ -290,8 +275,7 @@ struct amr_comm {
   int device = 0;
   int nranks = 1, rank = 0;
   std::mutex mu;                // every RCCL call on comm (amr_allgather*, the host collectives) and the staging buffer
-  void* stage = nullptr;        // device staging of amr_comm_allgather_host / allreduce_max
-  int64_t stage_bytes = 0;
+  DevBuf stage;                 // device staging of amr_comm_allgather_host / allreduce_max
 };
 
 namespace {
@@ -353,12 +337,21 @@ std::vector<PskAlloc> psk_allocs(const amr_psk_plan* pl) {
           {7, pl->max_streams * 12 + 64}};   // time-split: input peaks, flags, the flagged count
 }
 
+// the bytes of the buffers amr_psk_plan_create allocated, as they are now
+// (psk_allocs' eight, s1 / s3 at their current size)
+int64_t psk_scratch_bytes(const amr_psk_plan* pl) {
+  const amr_psk_plan::Mem& m = pl->mem;
+  return m.lo.bytes() + m.lo2.bytes() + m.s1_base.bytes() + m.s2.bytes() + m.s3_base.bytes() + m.words.bytes() +
+         m.flags.bytes() + m.split_peak.bytes();
+}
+
 // the most the plan can hold: `allocated` with s1 / s3 grown to the row
 // layout's size (on its first call) + the host-API staging (allocated on
 // the first amr_psk_demod_host)
 int64_t psk_max_bytes(const amr_psk_plan* pl, int64_t allocated) {
-  const int64_t have1 = pl->s1_bytes ? pl->s1_bytes : kFrontSlack * 8 + lane_s1_bytes(pl);
-  const int64_t have3 = pl->s3_bytes ? pl->s3_bytes : kFrontSlack * 8 + lane_s3_bytes(pl);
+  const int64_t s1b = pl->mem.s1_base.bytes(), s3b = pl->mem.s3_base.bytes();
+  const int64_t have1 = s1b ? s1b : kFrontSlack * 8 + lane_s1_bytes(pl);
+  const int64_t have3 = s3b ? s3b : kFrontSlack * 8 + lane_s3_bytes(pl);
   const int64_t grow = std::max<int64_t>(0, kFrontSlack * 8 + row_s1_bytes(pl) - have1) +
                        std::max<int64_t>(0, kFrontSlack * 8 + row_s3_bytes(pl) - have3);
   // + the host entries' staging: x (8 B per sample), outputs, the edge table
@@ -366,58 +359,46 @@ int64_t psk_max_bytes(const amr_psk_plan* pl, int64_t allocated) {
          pl->max_streams * 2 * pl->p.pad1 * 8;
 }
 
-// Grow one scratch buffer to `want` bytes.  The new block is allocated before
-// the old one is released, so a failed grow leaves the plan exactly as it was
-// (its pointers still valid for the layout that fits); only when that fails
-// is the old block freed first (tight memory), and if even then the new size
-// does not fit the old size is restored, or the buffer is left empty (NULL,
-// 0 bytes) -- run_psk re-checks the sizes before every launch and refuses a
-// plan whose buffers are too small instead of handing the kernels freed memory.
-int grow_scratch(amr_psk_plan* pl, double** base, int64_t* have, int64_t want) {
-  if (*have >= want && *base) return AMR_OK;
+// Grow one scratch buffer to `want` bytes: not DevBuf::reserve's policy.  The
+// new block is allocated before the old one is released, so a failed grow
+// leaves the plan exactly as it was (its pointers still valid for the layout
+// that fits); only when that fails is the old block freed first (tight
+// memory), and if even then the new size does not fit the old size is
+// restored, or the buffer is left empty (NULL, 0 bytes) -- run_psk re-checks
+// the sizes before every launch and refuses a plan whose buffers are too
+// small instead of handing the kernels freed memory.
+int grow_scratch(amr_psk_plan* pl, DevBuf& buf, int64_t want) {
+  if (buf.bytes() >= want && buf) return AMR_OK;
   static const bool fail_grow = [] {             // test hook: make every grow fail
     const char* e = std::getenv("AMR_TEST_FAIL_SCRATCH_GROW");
     return e && e[0] == '1';
   }();
   HIP_TRY(hipStreamSynchronize(pl->stream));     // queued work may still use the old block
-  double* nb = nullptr;
-  hipError_t e = fail_grow ? hipErrorOutOfMemory : hipMalloc(&nb, (size_t)want);
+  DevBuf nb;
+  hipError_t e = fail_grow ? hipErrorOutOfMemory : nb.reserve(want, nullptr);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    const int64_t old = *have;
-    HIP_TRY(hipFree(*base));
-    *base = nullptr;
-    *have = 0;
-    pl->scratch_bytes -= old;
-    e = fail_grow ? hipErrorOutOfMemory : hipMalloc(&nb, (size_t)want);
+    const int64_t old = buf.bytes();
+    HIP_TRY(buf.reset());
+    e = fail_grow ? hipErrorOutOfMemory : nb.reserve(want, nullptr);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      if (old > 0 && hipMalloc(base, (size_t)old) == hipSuccess) {
-        *have = old;
-        pl->scratch_bytes += old;
-      } else {
-        (void)hipGetLastError();
-        *base = nullptr;
-      }
+      if (old <= 0 || buf.reserve(old, nullptr) != hipSuccess) (void)hipGetLastError();
       return fail(AMR_E_NOMEM, "hipMalloc(" + std::to_string(want) + " B) for plan scratch: " + hipGetErrorString(e));
     }
-  } else {
-    HIP_TRY(hipFree(*base));
-    pl->scratch_bytes -= *have;
   }
-  *base = nb;
-  pl->scratch_bytes += want;
-  *have = want;
+  buf.swap(nb);
+  HIP_TRY(nb.reset());                           // the old block, if it was still held
   return AMR_OK;
 }
 
 // s1 / s3 at least b1 / b3 bytes (incl. the front slack); the kernel pointers
 // follow the (possibly new) blocks
 int ensure_scratch(amr_psk_plan* pl, int64_t b1, int64_t b3) {
-  int rc = grow_scratch(pl, &pl->s1_base, &pl->s1_bytes, b1);
-  if (rc == AMR_OK) rc = grow_scratch(pl, &pl->s3_base, &pl->s3_bytes, b3);
-  pl->s1 = pl->s1_base ? pl->s1_base + kFrontSlack : nullptr;
-  pl->s3 = pl->s3_base ? pl->s3_base + kFrontSlack : nullptr;
+  int rc = grow_scratch(pl, pl->mem.s1_base, b1);
+  if (rc == AMR_OK) rc = grow_scratch(pl, pl->mem.s3_base, b3);
+  pl->s1 = pl->mem.s1_base ? pl->mem.s1_base.as<double>() + kFrontSlack : nullptr;
+  pl->s3 = pl->mem.s3_base ? pl->mem.s3_base.as<double>() + kFrontSlack : nullptr;
   return rc;
 }
 }  // namespace
@@ -446,7 +427,6 @@ bool split_design_core(const Iir& bp, const Iir& lp, int64_t n, int64_t n_sym, i
 double f32_design(const Iir& lp);
 int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, int64_t L,
                         double* ebound = nullptr);
-int ensure(void** p, int64_t* have, int64_t need);
 int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
                    uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx);
 }  // namespace
@@ -502,17 +482,13 @@ int amr_device_synchronize(void) {
   return AMR_OK;
 }
 
+// set device, drain the stream, drop the gather gate; then the buffers; then events and the stream
 static void plan_free(amr_psk_plan* pl) {
   if (!pl) return;
   (void)hipSetDevice(pl->device);
   if (pl->stream) (void)hipStreamSynchronize(pl->stream);
   gate_free(pl->gate);
-  for (auto* p : {(void*)pl->lo, (void*)pl->lo2, (void*)pl->s1_base, (void*)pl->s2, (void*)pl->s3_base, (void*)pl->words, (void*)pl->flags,
-                  (void*)pl->split_peak, (void*)pl->split_tab, (void*)pl->split_zs, (void*)pl->strict_tab,
-                  (void*)pl->strict_bnd, (void*)pl->strict_sc,
-                  pl->d_x, (void*)pl->d_out, (void*)pl->d_len, (void*)pl->d_sync, (void*)pl->d_edge, (void*)pl->d_fec,
-                  (void*)pl->d_fec_len, (void*)pl->d_crc})
-    if (p) (void)hipFree(p);
+  pl->mem = amr_psk_plan::Mem{};                 // frees every device buffer
   for (auto& e : pl->ev)
     for (auto& h : e)
       if (h) (void)hipEventDestroy(h);
@@ -569,25 +545,19 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
     if (f[0] == '1') pl->lp_exact_only = true;
   p.f32_margin = bp_nt == 9 && p.lp_sym ? f32_design(pl->lp) : 0.0;
 
-  void** ptrs[] = {(void**)&pl->lo, (void**)&pl->lo2, (void**)&pl->s1_base, (void**)&pl->s2, (void**)&pl->s3_base,
-                   (void**)&pl->words, (void**)&pl->flags, (void**)&pl->split_peak};
-  struct A { void** ptr; int64_t bytes; };
-  std::vector<A> allocs;
-  for (const PskAlloc& a : psk_allocs(pl)) allocs.push_back({ptrs[a.which], a.bytes});
-  for (const A& a : allocs) {
-    e = hipMalloc(a.ptr, (size_t)a.bytes);
+  amr_psk_plan::Mem& m = pl->mem;
+  DevBuf* const bufs[] = {&m.lo, &m.lo2, &m.s1_base, &m.s2, &m.s3_base, &m.words, &m.flags, &m.split_peak};
+  for (const PskAlloc& a : psk_allocs(pl)) {
+    e = bufs[a.which]->reserve(a.bytes, nullptr);
     if (e != hipSuccess) {
       plan_free(pl);
       return fail(AMR_E_NOMEM, "hipMalloc(" + std::to_string(a.bytes) + " B): " + hipGetErrorString(e));
     }
-    pl->scratch_bytes += a.bytes;
   }
-  pl->s1 = pl->s1_base + kFrontSlack;
-  pl->s3 = pl->s3_base + kFrontSlack;
-  pl->split_flag = reinterpret_cast<int32_t*>(pl->split_peak + max_streams);
+  pl->s1 = m.s1_base.as<double>() + kFrontSlack;
+  pl->s3 = m.s3_base.as<double>() + kFrontSlack;
+  pl->split_flag = reinterpret_cast<int32_t*>(m.split_peak.as<unsigned long long>() + max_streams);
   pl->split_count = pl->split_flag + max_streams;
-  pl->s1_bytes = kFrontSlack * 8 + lane_s1_bytes(pl);
-  pl->s3_bytes = kFrontSlack * 8 + lane_s3_bytes(pl);
   {
     // device LO layout [n][4] = (lo_re, -(0*lo_im), lo_im, 0*lo_re): per sample and
     // component the (multiplier, addend) pair of numpy's complex multiply
@@ -598,13 +568,14 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
       lo_dev[4 * i + 2] = lo4[4 * i + 1];
       lo_dev[4 * i + 3] = lo4[4 * i + 3];
     }
-    e = hipMemcpy(pl->lo, lo_dev.data(), (size_t)(n * 4 * sizeof(double)), hipMemcpyHostToDevice);
+    e = hipMemcpy(m.lo.get(), lo_dev.data(), (size_t)(n * 4 * sizeof(double)), hipMemcpyHostToDevice);
     // [2][n]: the multipliers alone (K2q's main-body mixer, psk_kernels.hip)
     for (int64_t i = 0; i < n; ++i) {
       lo_dev[(size_t)i] = lo4[4 * i + 0];
       lo_dev[(size_t)(n + i)] = lo4[4 * i + 1];
     }
-    if (e == hipSuccess) e = hipMemcpy(pl->lo2, lo_dev.data(), (size_t)(n * 2 * sizeof(double)), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+      e = hipMemcpy(m.lo2.get(), lo_dev.data(), (size_t)(n * 2 * sizeof(double)), hipMemcpyHostToDevice);
   }
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
@@ -622,7 +593,7 @@ int amr_psk_plan_destroy(amr_psk_plan* plan) {
 int64_t amr_psk_plan_out_capacity(const amr_psk_plan* plan) { return plan ? plan->out_cap : -1; }
 int64_t amr_psk_plan_scratch_bytes(const amr_psk_plan* plan) {
   if (!plan) return -1;
-  return psk_max_bytes(plan, plan->scratch_bytes);
+  return psk_max_bytes(plan, psk_scratch_bytes(plan));
 }
 
 int64_t amr_psk_plan_bytes_estimate(int kind, int64_t n, int64_t sps, int64_t first, int bp_nt, int lp_nt,
@@ -733,12 +704,10 @@ int amr_psk_split_symbols_host(amr_psk_plan* plan, const void* x, int dtype, int
   if (chunk < 0 || (chunk > 0 && chunk < kSplitConvMinL && split_conv_on(plan)))
     return fail(AMR_E_INVALID, "amr_psk_split_symbols_host: chunk must be 0 (the plan's) or >= 128 with the convolution starts");
   const int64_t n = plan->p.n, es = dtype_size(dtype);
-  int64_t have = plan->d_x_bytes;
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  if (int rc = ensure(&plan->d_x, &have, B * n * es)) return rc;
-  plan->d_x_bytes = have;
-  if (int rc = copy_batch_h2d(plan->d_x, x, n * es, x_stride * es, B, plan->stream)) return rc;
-  if (int rc = run_psk_split_front(plan, plan->d_x, dtype, B, n, chunk)) return rc;
+  HIP_TRY(plan->mem.d_x.reserve(B * n * es, plan->stream));
+  void* const d_x = plan->mem.d_x.get();
+  if (int rc = copy_batch_h2d(d_x, x, n * es, x_stride * es, B, plan->stream)) return rc;
+  if (int rc = run_psk_split_front(plan, d_x, dtype, B, n, chunk)) return rc;
   HIP_TRY(hipStreamSynchronize(plan->stream));
   HIP_TRY(hipMemcpy(sym, plan->s1, (size_t)(B * plan->p.n_sym * 2 * 8), hipMemcpyDeviceToHost));
   return AMR_OK;
@@ -758,29 +727,25 @@ int amr_psk_split_bounds_host(amr_psk_plan* plan, const void* x, int dtype, int6
   if (plan->p.n_bits < 1 || plan->p.n_words < 1)
     return fail(AMR_E_INVALID, "amr_psk_split_bounds_host: this plan has no decision bits");
   const int64_t n = plan->p.n, es = dtype_size(dtype), S = plan->p.n_sym;
-  int64_t have = plan->d_x_bytes;
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  if (int rc = ensure(&plan->d_x, &have, B * n * es)) return rc;
-  plan->d_x_bytes = have;
-  double* stage = nullptr;
-  HIP_TRY(hipMalloc((void**)&stage, (size_t)(B * (S + 4) * 8)));
-  int rc = copy_batch_h2d(plan->d_x, x, n * es, x_stride * es, B, plan->stream);
-  if (!rc) rc = run_psk_split_front(plan, plan->d_x, dtype, B, n, 0, stage);
-  if (!rc) {
-    std::vector<double> h((size_t)(B * (S + 4)));
-    if (hipStreamSynchronize(plan->stream) != hipSuccess ||
-        hipMemcpy(sym, plan->s1, (size_t)(B * S * 2 * 8), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(h.data(), stage, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(AMR_E_HIP, "amr_psk_split_bounds_host: copy failed");
-    } else {
-      for (int64_t i = 0; i < B; ++i) {
-        std::memcpy(ebound + i * S, h.data() + i * (S + 4), (size_t)S * 8);
-        std::memcpy(scalars + i * 4, h.data() + i * (S + 4) + S, 32);
-      }
-    }
+  HIP_TRY(plan->mem.d_x.reserve(B * n * es, plan->stream));
+  void* const d_x = plan->mem.d_x.get();
+  DevBuf stage;
+  HIP_TRY(stage.reserve(B * (S + 4) * 8, nullptr));
+  int rc = copy_batch_h2d(d_x, x, n * es, x_stride * es, B, plan->stream);
+  if (!rc) rc = run_psk_split_front(plan, d_x, dtype, B, n, 0, stage.as<double>());
+  std::vector<double> h((size_t)(B * (S + 4)));
+  // (the wait also on a failed launch: queued work may write `stage`, freed on return)
+  if (hipStreamSynchronize(plan->stream) != hipSuccess && !rc)
+    rc = fail(AMR_E_HIP, "amr_psk_split_bounds_host: copy failed");
+  if (rc) return rc;
+  if (hipMemcpy(sym, plan->s1, (size_t)(B * S * 2 * 8), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(h.data(), stage.get(), h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(AMR_E_HIP, "amr_psk_split_bounds_host: copy failed");
+  for (int64_t i = 0; i < B; ++i) {
+    std::memcpy(ebound + i * S, h.data() + i * (S + 4), (size_t)S * 8);
+    std::memcpy(scalars + i * 4, h.data() + i * (S + 4) + S, 32);
   }
-  (void)hipFree(stage);
-  return rc;
+  return AMR_OK;
 }
 
 int amr_psk_plan_set_split_strict(amr_psk_plan* plan, int mode) {
@@ -899,7 +864,7 @@ int amr_psk_plan_exact_streams(amr_psk_plan* plan, int64_t* count) {
     }
   }
   std::vector<int32_t> fl((size_t)plan->groups * kWave);
-  HIP_TRY(hipMemcpy(fl.data(), plan->flags, fl.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fl.data(), plan->mem.flags.as<int32_t>(), fl.size() * 4, hipMemcpyDeviceToHost));
   int64_t c = 0;
   for (int64_t i = 0; i < plan->last_exact; ++i) c += fl[(size_t)i] != 0;
   *count = c;
@@ -942,7 +907,7 @@ bool split_design_core(const Iir& bp, const Iir& lp, int64_t n, int64_t n_sym, i
 // AMR_PSK_SPLIT_CONV=0: the w1-step warm-ups instead of KS0's convolution
 bool split_conv_on(const amr_psk_plan* pl) {
   static const bool conv_env = [] { const char* e = std::getenv("AMR_PSK_SPLIT_CONV"); return !(e && e[0] == '0'); }();
-  return conv_env && pl->split_tab && pl->bp.nt == 9;
+  return conv_env && pl->mem.split_tab.as<double>() && pl->bp.nt == 9;
 }
 // the strict bound for this plan's split calls: amr_psk_plan_set_split_strict,
 // else AMR_PSK_SPLIT_STRICT=1 (off by default: DESIGN.md §3.3)
@@ -972,15 +937,15 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
   sp.c2 = (pl->p.m2 + sp.L - 1) / sp.L;
   sp.kappa = pl->split_kappa;
   sp.y1 = pl->s1;
-  sp.f = pl->s2;
+  sp.f = pl->mem.s2.as<double>();
   sp.y3 = pl->s3;
   sp.sym = pl->s1;
-  sp.peak = pl->split_peak;
+  sp.peak = pl->mem.split_peak.as<unsigned long long>();
   sp.flag = pl->split_flag;
   sp.count = pl->split_count;
-  sp.ktab = pl->split_tab;
-  sp.z0tab = pl->split_tab ? pl->split_tab + (size_t)sp.w1 * 8 : nullptr;
-  sp.zs = pl->split_zs;
+  sp.ktab = pl->mem.split_tab.as<double>();
+  sp.z0tab = pl->mem.split_tab ? pl->mem.split_tab.as<double>() + (size_t)sp.w1 * 8 : nullptr;
+  sp.zs = pl->mem.split_zs.as<double>();
   pl->split_L = sp.L;
   // (a diagnostic's explicit chunk runs as given, without the strict
   // bookkeeping; fsk_api.cpp fsk_split_params likewise rounds only its own chunk)
@@ -992,9 +957,9 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
     sp.c2 = (pl->p.m2 + sp.L - 1) / sp.L;
     pl->split_L = sp.L;
     sp.strict = 1;
-    sp.bnd = pl->strict_bnd;
-    sp.sb = strict_bp_view(d, pl->strict_tab);
-    sp.lpc = pl->strict_tab + strict_bp_doubles(d);
+    sp.bnd = pl->mem.strict_bnd.as<unsigned long long>();
+    sp.sb = strict_bp_view(d, pl->mem.strict_tab.as<double>());
+    sp.lpc = pl->mem.strict_tab.as<double>() + strict_bp_doubles(d);
     sp.c3 = d.c3;
     sp.lp_tail = d.lp_tail;
     sp.lp_rad = d.lp_rad;
@@ -1008,23 +973,15 @@ PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
 // the strict scratch for B streams of this call's geometry
 int ensure_strict_sc(amr_psk_plan* pl, PskSplit& sp, int64_t B) {
   if (!sp.strict) return AMR_OK;
-  const int64_t need = B * sp.rows.sstride * 8;
-  if (pl->strict_sc_bytes < need || !pl->strict_sc) {
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    if (pl->strict_sc) HIP_TRY(hipFree(pl->strict_sc));
-    pl->strict_sc = nullptr;
-    pl->strict_sc_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&pl->strict_sc, (size_t)need));
-    pl->strict_sc_bytes = need;
-  }
-  sp.rows.sc = pl->strict_sc;
+  HIP_TRY(pl->mem.strict_sc.reserve(B * sp.rows.sstride * 8, pl->stream));
+  sp.rows.sc = pl->mem.strict_sc.as<double>();
   return AMR_OK;
 }
 // the strict mode's design and device tables, on the first strict call
 int strict_prepare(amr_psk_plan* pl) {
   if (pl->strict_designed) return AMR_OK;
   pl->strict_designed = true;
-  if (!pl->split_ok || !pl->split_tab) return AMR_OK;
+  if (!pl->split_ok || !pl->mem.split_tab) return AMR_OK;
   const int64_t w = pl->split_w1;
   std::vector<double> tab((size_t)(2 * w + 1) * 8);
   split_state_tables(pl->bp, w, tab.data(), tab.data() + (size_t)w * 8);
@@ -1034,9 +991,9 @@ int strict_prepare(amr_psk_plan* pl) {
   std::vector<double> dev;
   strict_bp_append(pl->sdes, dev);
   dev.insert(dev.end(), pl->sdes.lpc.begin(), pl->sdes.lpc.end());
-  HIP_TRY(hipMalloc((void**)&pl->strict_tab, dev.size() * 8));
-  HIP_TRY(hipMemcpy(pl->strict_tab, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&pl->strict_bnd, (size_t)pl->max_streams * 64));
+  HIP_TRY(pl->mem.strict_tab.reserve((int64_t)dev.size() * 8, nullptr));
+  HIP_TRY(hipMemcpy(pl->mem.strict_tab.get(), dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(pl->mem.strict_bnd.reserve(pl->max_streams * 64, nullptr));
   pl->strict_ok = true;
   return AMR_OK;
 }
@@ -1065,23 +1022,15 @@ void split_design(amr_psk_plan* pl) {
   const int64_t w = pl->split_w1;
   std::vector<double> tab((size_t)(2 * w + 1) * 8);
   split_state_tables(pl->bp, w, tab.data(), tab.data() + (size_t)w * 8);
-  if (hipMalloc((void**)&pl->split_tab, tab.size() * 8) != hipSuccess ||
-      hipMemcpy(pl->split_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-    if (pl->split_tab) (void)hipFree(pl->split_tab);
-    pl->split_tab = nullptr;
+  if (pl->mem.split_tab.reserve((int64_t)tab.size() * 8, nullptr) != hipSuccess ||
+      hipMemcpy(pl->mem.split_tab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)pl->mem.split_tab.reset();
     (void)hipGetLastError();
   }
 }
 int ensure_split_zs(amr_psk_plan* pl, const PskSplit& sp, int64_t B) {
   if (!sp.conv) return AMR_OK;
-  const int64_t need = B * sp.c1 * 8 * 8;
-  if (pl->split_zs_bytes >= need && pl->split_zs) return AMR_OK;
-  HIP_TRY(hipStreamSynchronize(pl->stream));
-  if (pl->split_zs) HIP_TRY(hipFree(pl->split_zs));
-  pl->split_zs = nullptr;
-  pl->split_zs_bytes = 0;
-  HIP_TRY(hipMalloc((void**)&pl->split_zs, (size_t)need));
-  pl->split_zs_bytes = need;
+  HIP_TRY(pl->mem.split_zs.reserve(B * sp.c1 * 8 * 8, pl->stream));
   return AMR_OK;
 }
 
@@ -1153,14 +1102,16 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
   b.dtype = dtype;
   b.n_streams = B;
   b.inflight = pl->inflight;
-  b.lo = pl->lo;
-  b.lo2 = pl->lo2;
+  b.lo = pl->mem.lo.as<double>();
+  b.lo2 = pl->mem.lo2.as<double>();
   b.s1 = pl->s1;
-  b.s2 = pl->s2;
+  b.s2 = pl->mem.s2.as<double>();
   b.s3 = pl->s3;
-  b.words = pl->words;
-  b.flags = pl->flags;
-  b.bp_flags = pl->flags + pl->groups * kWave;
+  uint32_t* const words = pl->mem.words.as<uint32_t>();
+  int32_t* const flags = pl->mem.flags.as<int32_t>();
+  b.words = words;
+  b.flags = flags;
+  b.bp_flags = flags + pl->groups * kWave;
   b.out = d_out;
   b.out_stride = out_stride;
   b.out_len = d_len;
@@ -1195,8 +1146,9 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     PskSplit sp = split_params(pl, B, 0);
     if (int rc = ensure_split_zs(pl, sp, B)) return rc;
     if (int rc = ensure_strict_sc(pl, sp, B)) return rc;
-    sp.zs = pl->split_zs;
-    HIP_TRY(hipMemsetAsync(pl->split_peak, 0, (size_t)pl->max_streams * 12 + 4, st));   // peaks, flags, count
+    sp.zs = pl->mem.split_zs.as<double>();
+    // peaks, flags, count
+    HIP_TRY(hipMemsetAsync(pl->mem.split_peak.get(), 0, (size_t)pl->max_streams * 12 + 4, st));
     if (sp.strict) HIP_TRY(hipMemsetAsync(sp.bnd, 0, (size_t)B * 64, st));
     pl->last_strict = sp.strict != 0;
     HIP_TRY(mark(AMR_T_BANDPASS, 0));
@@ -1208,7 +1160,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
     HIP_TRY(launch_psk_split_slice(b, pl->p, sp, st));
     HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
-    HIP_TRY(launch_sync_pack(pl->words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
     HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
     // the serial row kernels over the whole batch, each exiting at once while
     // no stream was flagged (the count on the device; no host round trip)
@@ -1217,15 +1169,15 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 0));
     HIP_TRY(launch_psk_bandpass(g, pl->p, pl->bp, st));
     if (pl->lp_exact_only) {
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->flags, 1, (size_t)B, st));
+      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
     } else {
       HIP_TRY(launch_psk_lowpass_fwd(g, pl->p, pl->lp, st));
       HIP_TRY(launch_psk_lowpass_bwd(g, pl->p, pl->lp, st));
     }
     HIP_TRY(launch_psk_lowpass_exact(g, pl->p, pl->lp, st));
     HIP_TRY(launch_psk_slice(g, pl->p, st));
-    HIP_TRY(launch_sync_pack_gated(pl->words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync,
-                                   pl->split_count, st));
+    HIP_TRY(launch_sync_pack_gated(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, pl->split_count,
+                                   st));
     HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 1));
   } else if (lane) {
     // AMR_PSK_F32F=1 (an A/B, off by default): the float32 hand-off of f
@@ -1235,7 +1187,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     // flags 3.6 % of the benchmark's streams, whose groups the fix-up and K3x
     // then redo: 13.9 vs 3.72-3.79 ms/step (profiles/r05_psk_f32f_ab.txt)
     static const bool f32f_env = [] { const char* e = std::getenv("AMR_PSK_F32F"); return e && e[0] == '1'; }();
-    b.fpeak = reinterpret_cast<double*>(pl->split_peak);
+    b.fpeak = reinterpret_cast<double*>(pl->mem.split_peak.as<unsigned long long>());
     b.f32f = f32f_env && pl->p.f32_margin > 0.0 && !pl->lp_exact_only && psk_lane_fused(b, pl->p) ? 1 : 0;
     pl->last_f32f = b.f32f != 0;
     HIP_TRY(mark(AMR_T_BANDPASS, 0));
@@ -1243,7 +1195,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_BANDPASS, 1));
     bool sliced = false;                        // the low-pass wrote the words itself (k_lp_lane FUSE)
     if (pl->lp_exact_only) {
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->flags, 1, (size_t)B, st));
+      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
     } else {
       // forward + backward low-pass in one kernel: timed in the lowpass_fwd slot
       HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
@@ -1259,7 +1211,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
     HIP_TRY(launch_psk_slice(b, pl->p, st, sliced));   // then only the K3x streams
     HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
-    HIP_TRY(launch_sync_pack(pl->words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
     HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
   } else {
     HIP_TRY(mark(AMR_T_BANDPASS, 0));
@@ -1267,7 +1219,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_BANDPASS, 1));
     if (pl->lp_exact_only) {
       // every stream takes the exact complex path
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->flags, 1, (size_t)B, st));
+      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
     } else {
       HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
       HIP_TRY(launch_psk_lowpass_fwd(b, pl->p, pl->lp, st));
@@ -1282,7 +1234,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
     HIP_TRY(launch_psk_slice(b, pl->p, st));
     HIP_TRY(gate_wait(pl->gate, st));
-    HIP_TRY(launch_sync_pack(pl->words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
     HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
   }
   if (d_fec) {
@@ -1309,8 +1261,8 @@ int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B,
   b.x_stride = x_stride;
   b.dtype = dtype;
   b.n_streams = B;
-  b.lo = pl->lo;
-  b.lo2 = pl->lo2;
+  b.lo = pl->mem.lo.as<double>();
+  b.lo2 = pl->mem.lo2.as<double>();
   const int saved = pl->strict_mode;
   if (ebound) {
     pl->strict_mode = 1;
@@ -1321,28 +1273,19 @@ int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B,
   if (ebound && !sp.strict) return fail(AMR_E_INVALID, "no strict bound for this plan (no convolution starts or design)");
   if (int rc = ensure_split_zs(pl, sp, B)) return rc;
   if (int rc = ensure_strict_sc(pl, sp, B)) return rc;
-  sp.zs = pl->split_zs;
-  HIP_TRY(hipMemsetAsync(pl->split_peak, 0, (size_t)pl->max_streams * 12 + 4, pl->stream));
+  sp.zs = pl->mem.split_zs.as<double>();
+  HIP_TRY(hipMemsetAsync(pl->mem.split_peak.get(), 0, (size_t)pl->max_streams * 12 + 4, pl->stream));
   if (sp.strict) HIP_TRY(hipMemsetAsync(sp.bnd, 0, (size_t)B * 64, pl->stream));
   HIP_TRY(launch_psk_split_bp(b, pl->p, pl->bp, sp, pl->stream));
   HIP_TRY(launch_psk_split_lp(b, pl->p, pl->lp, sp, pl->stream));
   if (ebound) {
-    b.words = pl->words;
+    b.words = pl->mem.words.as<uint32_t>();
     HIP_TRY(launch_psk_split_slice(b, pl->p, sp, pl->stream));
     // e(k) and the scalars of every stream, packed [B][S + 4]
     const int64_t S = pl->p.n_sym;
     HIP_TRY(hipMemcpy2DAsync(ebound, (size_t)(S + 4) * 8, sp.rows.sc + strict_off_e(sp), (size_t)sp.rows.sstride * 8,
                              (size_t)(S + 4) * 8, (size_t)B, hipMemcpyDeviceToDevice, pl->stream));
   }
-  return AMR_OK;
-}
-
-int ensure(void** p, int64_t* have, int64_t need) {
-  if (*have >= need && *p) return AMR_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  HIP_TRY(hipMalloc(p, (size_t)need));
-  *have = need;
   return AMR_OK;
 }
 
@@ -1399,6 +1342,17 @@ int amr_psk_demod_host_edges(amr_psk_plan* plan, const void* x, int dtype, int64
 }  // extern "C"
 
 namespace {
+// the host entries' staging: the input at max_streams x n x 8 B (a grow waits
+// for the stream: queued work may still read the old block) and the output
+// group, whole or not at all
+int psk_host_staging(amr_psk_plan* pl) {
+  const int64_t ms = pl->max_streams;
+  HIP_TRY(pl->mem.d_x.reserve(ms * pl->p.n * 8, pl->stream));
+  // (the inner parentheses keep the braces' commas from splitting the macro's argument)
+  HIP_TRY((reserve_all({{pl->mem.d_out, ms * pl->out_cap}, {pl->mem.d_len, ms * 8}, {pl->mem.d_sync, ms * 8}},
+                       pl->stream)));
+  return AMR_OK;
+}
 int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
                    uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
   if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
@@ -1416,29 +1370,24 @@ int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int6
   if (B == 0) return AMR_OK;
   const int64_t n = plan->p.n;
   const int64_t cap = plan->out_cap;
-  int rc = ensure(&plan->d_x, &plan->d_x_bytes, plan->max_streams * n * 8);
-  if (rc) return rc;
-  if (!plan->d_out) {
-    HIP_TRY(hipMalloc(&plan->d_out, (size_t)(plan->max_streams * cap)));
-    HIP_TRY(hipMalloc(&plan->d_len, (size_t)plan->max_streams * 8));
-    HIP_TRY(hipMalloc(&plan->d_sync, (size_t)plan->max_streams * 8));
-  }
-  rc = copy_batch_h2d(plan->d_x, x, n * es, x_stride * es, B, plan->stream);
+  amr_psk_plan::Mem& m = plan->mem;
+  if (int rc = psk_host_staging(plan)) return rc;
+  int rc = copy_batch_h2d(m.d_x.get(), x, n * es, x_stride * es, B, plan->stream);
   if (rc) return rc;
   const double* d_edge = nullptr;
   if (edges) {
     const int64_t eb = B * 2 * plan->p.pad1 * 8;
-    if ((rc = ensure((void**)&plan->d_edge, &plan->d_edge_bytes, plan->max_streams * 2 * plan->p.pad1 * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(plan->d_edge, edges, (size_t)eb, hipMemcpyHostToDevice, plan->stream));
-    d_edge = plan->d_edge;
+    HIP_TRY(m.d_edge.reserve(plan->max_streams * 2 * plan->p.pad1 * 8, plan->stream));
+    HIP_TRY(hipMemcpyAsync(m.d_edge.get(), edges, (size_t)eb, hipMemcpyHostToDevice, plan->stream));
+    d_edge = m.d_edge.as<double>();
   }
-  rc = run_psk(plan, plan->d_x, dtype, B, n, plan->d_out, cap, plan->d_len, plan->d_sync, nullptr, 0, nullptr,
-               nullptr, d_edge);
+  rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
+               m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge);
   if (rc) return rc;
-  rc = copy_batch_d2h(out, out_stride, plan->d_out, cap, out_stride < cap ? out_stride : cap, B, plan->stream);
+  rc = copy_batch_d2h(out, out_stride, m.d_out.get(), cap, out_stride < cap ? out_stride : cap, B, plan->stream);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out_len, plan->d_len, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipMemcpyAsync(sync_idx, plan->d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(hipMemcpyAsync(out_len, m.d_len.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(hipMemcpyAsync(sync_idx, m.d_sync.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipStreamSynchronize(plan->stream));
   return AMR_OK;
 }
@@ -1466,31 +1415,24 @@ int amr_psk_demod_host_async(amr_psk_plan* plan, const void* x, int dtype, int64
   if (B == 0) return AMR_OK;
   const int64_t n = plan->p.n;
   const int64_t cap = plan->out_cap;
-  if (!plan->d_x || plan->d_x_bytes < plan->max_streams * n * 8) {
-    HIP_TRY(hipStreamSynchronize(plan->stream));          // a previous staging buffer may still be read
-    if (int rc = ensure(&plan->d_x, &plan->d_x_bytes, plan->max_streams * n * 8)) return rc;
-  }
-  if (!plan->d_out) {
-    HIP_TRY(hipMalloc(&plan->d_out, (size_t)(plan->max_streams * cap)));
-    HIP_TRY(hipMalloc(&plan->d_len, (size_t)plan->max_streams * 8));
-    HIP_TRY(hipMalloc(&plan->d_sync, (size_t)plan->max_streams * 8));
-  }
+  amr_psk_plan::Mem& m = plan->mem;
+  if (int rc = psk_host_staging(plan)) return rc;
   hipStream_t st = plan->stream;
   if (x_stride == n)
-    HIP_TRY(hipMemcpyAsync(plan->d_x, x, (size_t)(B * n * es), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.d_x.get(), x, (size_t)(B * n * es), hipMemcpyHostToDevice, st));
   else
-    HIP_TRY(hipMemcpy2DAsync(plan->d_x, (size_t)(n * es), x, (size_t)(x_stride * es), (size_t)(n * es), (size_t)B,
+    HIP_TRY(hipMemcpy2DAsync(m.d_x.get(), (size_t)(n * es), x, (size_t)(x_stride * es), (size_t)(n * es), (size_t)B,
                              hipMemcpyHostToDevice, st));
-  if (int rc = run_psk(plan, plan->d_x, dtype, B, n, plan->d_out, cap, plan->d_len, plan->d_sync, nullptr, 0,
-                       nullptr, nullptr))
+  if (int rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
+                       m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr))
     return rc;
   if (out_stride == cap)
-    HIP_TRY(hipMemcpyAsync(out, plan->d_out, (size_t)(B * cap), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, m.d_out.get(), (size_t)(B * cap), hipMemcpyDeviceToHost, st));
   else
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, plan->d_out, (size_t)cap, (size_t)std::min(out_stride, cap),
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, m.d_out.get(), (size_t)cap, (size_t)std::min(out_stride, cap),
                              (size_t)B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_len, plan->d_len, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sync_idx, plan->d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out_len, m.d_len.get(), (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sync_idx, m.d_sync.get(), (size_t)B * 8, hipMemcpyDeviceToHost, st));
   return AMR_OK;
 }
 
@@ -1534,27 +1476,27 @@ int amr_fec_decode_host(const uint8_t* in, int64_t in_stride, const int64_t* in_
     maxlen = in_len[i] > maxlen ? in_len[i] : maxlen;
   }
   if (dev < 0 || dev >= 64) return fail(AMR_E_INVALID, "device ordinal out of range");
-  HostStaging& hs = g_staging[dev];
+  HostStaging& hs = host_staging(dev);
   std::lock_guard<std::mutex> lk(hs.mu);
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("amr_fec_decode_host: ") + hipGetErrorString(e));
+  };
   uint8_t *d_in = nullptr, *d_out = nullptr;
   int64_t *d_in_len = nullptr, *d_out_len = nullptr;
   int32_t* d_crc = nullptr;
   const int64_t stride = maxlen > 0 ? maxlen : 1;
-  hipError_t e = staging_get(hs, 0, n * stride, (void**)&d_in);
-  if (e == hipSuccess) e = staging_get(hs, 1, n * stride, (void**)&d_out);
-  if (e == hipSuccess) e = staging_get(hs, 2, n * 8, (void**)&d_in_len);
-  if (e == hipSuccess) e = staging_get(hs, 3, n * 8, (void**)&d_out_len);
-  if (e == hipSuccess) e = staging_get(hs, 4, n * 4, (void**)&d_crc);
-  if (e == hipSuccess && maxlen > 0)
-    e = memcpy_rows(d_in, stride, in, in_stride, maxlen, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_in_len, in_len, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_fec_decode(d_in, stride, d_in_len, n, d_out, stride, d_out_len, d_crc, tab, x2n, 0);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess && maxlen > 0)
-    e = memcpy_rows(out, out_stride, d_out, stride, maxlen, n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_len, d_out_len, (size_t)n * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(crc_ok, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(AMR_E_HIP, std::string("amr_fec_decode_host: ") + hipGetErrorString(e));
+  HIP_TRY_ELSE(staging_get(hs, 0, n * stride, (void**)&d_in), bad);
+  HIP_TRY_ELSE(staging_get(hs, 1, n * stride, (void**)&d_out), bad);
+  HIP_TRY_ELSE(staging_get(hs, 2, n * 8, (void**)&d_in_len), bad);
+  HIP_TRY_ELSE(staging_get(hs, 3, n * 8, (void**)&d_out_len), bad);
+  HIP_TRY_ELSE(staging_get(hs, 4, n * 4, (void**)&d_crc), bad);
+  if (maxlen > 0) HIP_TRY_ELSE(memcpy_rows(d_in, stride, in, in_stride, maxlen, n, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(hipMemcpy(d_in_len, in_len, (size_t)n * 8, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(launch_fec_decode(d_in, stride, d_in_len, n, d_out, stride, d_out_len, d_crc, tab, x2n, 0), bad);
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  if (maxlen > 0) HIP_TRY_ELSE(memcpy_rows(out, out_stride, d_out, stride, maxlen, n, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(out_len, d_out_len, (size_t)n * 8, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(crc_ok, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost), bad);
   return AMR_OK;
 }
 
@@ -1587,23 +1529,20 @@ int amr_psk_slice_host(int kind, const double* sym, int64_t n_streams, int64_t n
     for (int64_t k = 0; k < n_sym; ++k)
       for (int c = 0; c < 2; ++c)
         h[(size_t)(((s >> 6) * 2 + c) * n_sym + k) * 64 + (s & 63)] = sym[(s * n_sym + k) * 2 + c];
-  double* d_sym = nullptr;
-  uint32_t* d_words = nullptr;
-  hipError_t e = hipMalloc(&d_sym, h.size() * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_words, (size_t)(n_streams * p.n_words) * 4);
-  if (e == hipSuccess) e = hipMemcpy(d_sym, h.data(), h.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    PskBuffers b{};
-    b.n_streams = n_streams;
-    b.s1 = d_sym;
-    b.words = d_words;
-    e = launch_psk_slice(b, p, nullptr);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(words, d_words, (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost);
-  if (d_sym) (void)hipFree(d_sym);
-  if (d_words) (void)hipFree(d_words);
-  if (e != hipSuccess) return fail(AMR_E_HIP, std::string("amr_psk_slice_host: ") + hipGetErrorString(e));
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("amr_psk_slice_host: ") + hipGetErrorString(e));
+  };
+  DevBuf d_sym, d_words;
+  HIP_TRY_ELSE(d_sym.reserve((int64_t)h.size() * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_words.reserve(n_streams * p.n_words * 4, nullptr), bad);
+  HIP_TRY_ELSE(hipMemcpy(d_sym.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice), bad);
+  PskBuffers b{};
+  b.n_streams = n_streams;
+  b.s1 = d_sym.as<double>();
+  b.words = d_words.as<uint32_t>();
+  HIP_TRY_ELSE(launch_psk_slice(b, p, nullptr), bad);
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  HIP_TRY_ELSE(hipMemcpy(words, d_words.get(), (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost), bad);
   return AMR_OK;
 }
 
@@ -1649,26 +1588,26 @@ int amr_frame_parse_host(const uint8_t* in, int64_t in_stride, const int64_t* in
     maxlen = in_len[i] > maxlen ? in_len[i] : maxlen;
   }
   if (dev < 0 || dev >= 64) return fail(AMR_E_INVALID, "device ordinal out of range");
-  HostStaging& hs = g_staging[dev];
+  HostStaging& hs = host_staging(dev);
   std::lock_guard<std::mutex> lk(hs.mu);
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("amr_frame_parse_host: ") + hipGetErrorString(e));
+  };
   uint8_t* d_in = nullptr;
   int64_t* d_in_len = nullptr;
   int32_t* d_cnt = nullptr;
   amr_frame_rec* d_recs = nullptr;
   const int64_t stride = maxlen > 0 ? maxlen : 1;
-  hipError_t e = staging_get(hs, 0, n * stride, (void**)&d_in);
-  if (e == hipSuccess) e = staging_get(hs, 2, n * 8, (void**)&d_in_len);
-  if (e == hipSuccess) e = staging_get(hs, 4, n * 4, (void**)&d_cnt);
-  if (e == hipSuccess) e = staging_get(hs, 5, n * max_cands * (int64_t)sizeof(amr_frame_rec), (void**)&d_recs);
-  if (e == hipSuccess && maxlen > 0)
-    e = memcpy_rows(d_in, stride, in, in_stride, maxlen, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_in_len, in_len, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_frame_parse(d_in, stride, d_in_len, n, max_cands, d_cnt, d_recs, tab, x2n, 0);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(n_cands, d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess)
-    e = hipMemcpy(recs, d_recs, (size_t)(n * max_cands) * sizeof(amr_frame_rec), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(AMR_E_HIP, std::string("amr_frame_parse_host: ") + hipGetErrorString(e));
+  HIP_TRY_ELSE(staging_get(hs, 0, n * stride, (void**)&d_in), bad);
+  HIP_TRY_ELSE(staging_get(hs, 2, n * 8, (void**)&d_in_len), bad);
+  HIP_TRY_ELSE(staging_get(hs, 4, n * 4, (void**)&d_cnt), bad);
+  HIP_TRY_ELSE(staging_get(hs, 5, n * max_cands * (int64_t)sizeof(amr_frame_rec), (void**)&d_recs), bad);
+  if (maxlen > 0) HIP_TRY_ELSE(memcpy_rows(d_in, stride, in, in_stride, maxlen, n, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(hipMemcpy(d_in_len, in_len, (size_t)n * 8, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(launch_frame_parse(d_in, stride, d_in_len, n, max_cands, d_cnt, d_recs, tab, x2n, 0), bad);
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  HIP_TRY_ELSE(hipMemcpy(n_cands, d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(recs, d_recs, (size_t)(n * max_cands) * sizeof(amr_frame_rec), hipMemcpyDeviceToHost), bad);
   return AMR_OK;
 }
 
@@ -1771,7 +1710,7 @@ int amr_comm_destroy(amr_comm* comm) {
   if (!comm) return AMR_OK;
   (void)hipSetDevice(comm->device);
   if (comm->stream) (void)hipStreamSynchronize(comm->stream);
-  if (comm->stage) (void)hipFree(comm->stage);
+  (void)comm->stage.reset();
   if (comm->comm) ncclCommDestroy(comm->comm);
   if (comm->stream) (void)hipStreamDestroy(comm->stream);
   delete comm;
@@ -1807,20 +1746,6 @@ int amr_comm_world(const amr_comm* comm, int* nranks, int* rank) {
   return AMR_OK;
 }
 
-namespace {
-// the comm's device staging buffer, at least `bytes` (caller holds comm->mu)
-int comm_stage(amr_comm* c, int64_t bytes) {
-  if (c->stage_bytes >= bytes && c->stage) return AMR_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->stage) HIP_TRY(hipFree(c->stage));
-  c->stage = nullptr;
-  c->stage_bytes = 0;
-  HIP_TRY(hipMalloc(&c->stage, (size_t)bytes));
-  c->stage_bytes = bytes;
-  return AMR_OK;
-}
-}  // namespace
-
 int amr_comm_allgather_host(amr_comm* comm, const void* send, void* recv, int64_t bytes_per_rank) {
   if (!comm || bytes_per_rank < 0 || (bytes_per_rank && (!send || !recv)))
     return fail(AMR_E_INVALID, "amr_comm_allgather_host: bad argument");
@@ -1828,8 +1753,8 @@ int amr_comm_allgather_host(amr_comm* comm, const void* send, void* recv, int64_
   std::lock_guard<std::mutex> lk(comm->mu);
   HIP_TRY(hipSetDevice(comm->device));
   const int64_t total = bytes_per_rank * (1 + comm->nranks);     // [send | recv (world slots)]
-  if (int rc = comm_stage(comm, total)) return rc;
-  uint8_t* d_send = static_cast<uint8_t*>(comm->stage);
+  HIP_TRY(comm->stage.reserve(total, comm->stream));   // (caller holds comm->mu)
+  uint8_t* d_send = comm->stage.as<uint8_t>();
   uint8_t* d_recv = d_send + bytes_per_rank;
   HIP_TRY(hipMemcpyAsync(d_send, send, (size_t)bytes_per_rank, hipMemcpyHostToDevice, comm->stream));
   ncclResult_t r = ncclAllGather(d_send, d_recv, (size_t)bytes_per_rank, ncclUint8, comm->comm, comm->stream);
@@ -1844,8 +1769,8 @@ int amr_comm_allreduce_max(amr_comm* comm, double* values, int64_t count) {
   if (count == 0) return AMR_OK;
   std::lock_guard<std::mutex> lk(comm->mu);
   HIP_TRY(hipSetDevice(comm->device));
-  if (int rc = comm_stage(comm, count * 8)) return rc;
-  double* d = static_cast<double*>(comm->stage);
+  HIP_TRY(comm->stage.reserve(count * 8, comm->stream));
+  double* d = comm->stage.as<double>();
   HIP_TRY(hipMemcpyAsync(d, values, (size_t)(count * 8), hipMemcpyHostToDevice, comm->stream));
   ncclResult_t r = ncclAllReduce(d, d, (size_t)count, ncclFloat64, ncclMax, comm->comm, comm->stream);
   if (r != ncclSuccess) return fail(AMR_E_RCCL, std::string("ncclAllReduce: ") + ncclGetErrorString(r));

@@ -57,3 +57,10 @@ int allgather_after(amr_comm* comm, const void* d_send, void* d_recv, int64_t by
       return ::amr::fail(e_ == hipErrorOutOfMemory ? AMR_E_NOMEM : AMR_E_HIP,                      \
                          std::string(#expr) + ": " + hipGetErrorString(e_));                      \
   } while (0)
+// the same early return for an entry that reports failures under its own
+// name and code: `on_fail` (a function or lambda int(hipError_t)) makes the return value
+#define HIP_TRY_ELSE(expr, on_fail)                                                                \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess) return on_fail(e_);                                                      \
+  } while (0)

@@ -22,6 +22,7 @@
 
 #include "amr_internal.h"
 #include "api_common.h"
+#include "dev_mem.h"
 #include "fsk_exact.h"
 #include "fft.h"
 #include "iir_design.h"
@@ -63,27 +64,24 @@ struct FftPlan {
   const double2* chirp = nullptr;    // Bluestein chirp, or all ones (six-step, plain epilogues)
   const double2* bhat = nullptr;     // FFT_M(bw) (two-pass Bluestein filter table)
   const double2* bhat_c = nullptr;   // conj(FFT_M(bw)) (six-step Bluestein: applied by the post kernel)
-  double2* s1 = nullptr;             // six-step scratch [max_batch][M] x 2
-  double2* s2 = nullptr;
   int64_t max_batch = 0;
-  std::vector<void*> allocs;
+  // what the plan owns on the device (freed with it; a plan's fsk_plan_free
+  // releases them with the plan's own buffers): the tables the pointers above
+  // look into, and the six-step scratch [max_batch][M] x 2
+  struct Mem {
+    std::vector<DevBuf> tables;
+    DevBuf s1, s2;
+  } mem;
 };
-
-void fft_plan_free(FftPlan& f) {
-  for (void* p : f.allocs)
-    if (p) (void)hipFree(p);
-  f.allocs.clear();
-  f.s1 = f.s2 = nullptr;
-}
 
 // device copy of interleaved host values
 hipError_t upload(FftPlan& f, const std::vector<double>& h, const double2** out) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, h.size() * 8 + 16);
+  DevBuf t;
+  hipError_t e = t.reserve((int64_t)h.size() * 8 + 16, nullptr);
   if (e != hipSuccess) return e;
-  f.allocs.push_back(p);
-  e = hipMemcpy(p, h.data(), h.size() * 8, hipMemcpyHostToDevice);
-  *out = static_cast<const double2*>(p);
+  e = hipMemcpy(t.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice);
+  *out = t.as<const double2>();
+  f.mem.tables.push_back(std::move(t));
   return e;
 }
 
@@ -114,16 +112,17 @@ int desc_init(FftPlan& f, FftDesc& d, int64_t L) {
 hipError_t six_fft(const FftPlan& f, const double2* in, double2* out, int64_t batch, bool inverse, hipStream_t st) {
   if (batch > f.max_batch) return hipErrorInvalidValue;
   const int64_t L1 = f.L1, L2 = f.L2;
+  double2 *const s1 = f.mem.s1.as<double2>(), *const s2 = f.mem.s2.as<double2>();
   // in[j1 + L1 j2] = [j2][j1] -> s1[j1][j2]
-  hipError_t e = launch_transpose(in, f.s1, L2, L1, batch, nullptr, nullptr, false, st);
+  hipError_t e = launch_transpose(in, s1, L2, L1, batch, nullptr, nullptr, false, st);
   // L2-point transforms of every row j1 -> s1[j1][k2]
-  if (e == hipSuccess) e = launch_fft(f.s1, f.s2, f.s1, f.d2, batch * L1, inverse, st);
+  if (e == hipSuccess) e = launch_fft(s1, s2, s1, f.d2, batch * L1, inverse, st);
   // times W_M^(j1 k2), -> s2[k2][j1]
-  if (e == hipSuccess) e = launch_transpose(f.s1, f.s2, L1, L2, batch, f.tw6_lo, f.tw6_hi, inverse, st);
+  if (e == hipSuccess) e = launch_transpose(s1, s2, L1, L2, batch, f.tw6_lo, f.tw6_hi, inverse, st);
   // L1-point transforms of every row k2 -> s2[k2][k1]
-  if (e == hipSuccess) e = launch_fft(f.s2, f.s1, f.s2, f.d1, batch * L2, inverse, st);
+  if (e == hipSuccess) e = launch_fft(s2, s1, s2, f.d1, batch * L2, inverse, st);
   // X[k2 + L2 k1] = out[k1][k2]
-  if (e == hipSuccess) e = launch_transpose(f.s2, out, L2, L1, batch, nullptr, nullptr, false, st);
+  if (e == hipSuccess) e = launch_transpose(s2, out, L2, L1, batch, nullptr, nullptr, false, st);
   return e;
 }
 
@@ -194,13 +193,8 @@ int fft_plan_init(FftPlan& f, int64_t n, hipStream_t st, int64_t max_batch) {
     HIP_TRY(upload(f, host, &t));
     f.tw6_lo = t;
     f.tw6_hi = t + 256;
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, (size_t)(max_batch * M * 16)));
-    f.allocs.push_back(p);
-    f.s1 = static_cast<double2*>(p);
-    HIP_TRY(hipMalloc(&p, (size_t)(max_batch * M * 16)));
-    f.allocs.push_back(p);
-    f.s2 = static_cast<double2*>(p);
+    HIP_TRY(f.mem.s1.reserve(max_batch * M * 16, nullptr));
+    HIP_TRY(f.mem.s2.reserve(max_batch * M * 16, nullptr));
   } else {
     if (int rc = desc_init(f, f.d, M)) return rc;
   }
@@ -231,16 +225,14 @@ int fft_plan_init(FftPlan& f, int64_t n, hipStream_t st, int64_t max_batch) {
   }
   const double2* bwd = nullptr;
   HIP_TRY(upload(f, bw, &bwd));
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, (size_t)M * sizeof(double2)));
-  f.allocs.push_back(p);
-  double2* bh = static_cast<double2*>(p);
+  f.mem.tables.emplace_back();
+  HIP_TRY(f.mem.tables.back().reserve(M * (int64_t)sizeof(double2), nullptr));
+  double2* bh = f.mem.tables.back().as<double2>();
   if (!f.six) {
-    double2* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (size_t)M * sizeof(double2)));
-    hipError_t e = launch_fft(bwd, tmp, bh, f.d, 1, false, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
+    DevBuf tmp;
+    HIP_TRY(tmp.reserve(M * (int64_t)sizeof(double2), nullptr));
+    hipError_t e = launch_fft(bwd, tmp.as<double2>(), bh, f.d, 1, false, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // before tmp is freed
     HIP_TRY(e);
     f.bhat = bh;
   } else {
@@ -332,14 +324,39 @@ struct amr_fsk_plan {
   FftPlan fft{};
   int64_t max_streams = 0;
   int64_t out_cap = 0;
-  // HBM scratch
-  // natural layout (p.lc.on == 0): z [B][n], u / v [B][M] (u also F1's
-  // checkpoint scratch).  Live-column layout (p.lc.on, amr_internal.h
-  // LiveCols): z = [B][L | D] (n per stream), u = C [B][nl * n2] -- also F1's
-  // checkpoint scratch and, on the host entries, the staged input -- and no v.
-  double2* z = nullptr;
-  double2* u = nullptr;
-  double2* v = nullptr;
+  // Every device buffer the plan owns (dev_mem.h DevBuf), in the sets the
+  // byte totals below sum (fsk_scratch_bytes, fsk_split_bytes,
+  // fsk_strict_bytes, fsk_out_staging_bytes); fsk_plan_free releases them
+  // together, after the streams are drained and before they are destroyed.
+  struct Mem {
+    // HBM scratch, allocated with the plan (dd: by the first host entry)
+    // natural layout (p.lc.on == 0): z [B][n], u / v [B][M] (u also F1's
+    // checkpoint scratch).  Live-column layout (p.lc.on, amr_internal.h
+    // LiveCols): z = [B][L | D] (n per stream), u = C [B][nl * n2] -- also F1's
+    // checkpoint scratch and, on the host entries, the staged input -- and no v.
+    DevBuf z, u, v;
+    DevBuf dd;       // see keep_z below
+    DevBuf cmp;      // [B][bits_stride] packed compare bits (fft.h fft_bits_stride)
+    DevBuf words;    // [B][n_words]
+    // the exact path (fsk_exact_kernels.hip)
+    DevBuf xflags;   // [B / 32] F2's flags, bit s of word s / 32 (cleared by F1 every batch)
+    DevBuf amb;      // [B] F1's ambiguity scale per stream
+    DevBuf xlist;    // [B] flagged ordinal -> stream, then [1] the count
+    DevBuf xslots;   // [n_slots][slot_doubles] envelope scratch
+    DevBuf xbits;    // [B][bits_stride] the flagged streams' exact compare bits
+    DevBuf xpool;    // pocketfft's twiddle / chirp tables of length n
+    DevBuf xL;       // pocketfft's plans of length n (device copy)
+    // the time-split F1, on the first split call: the forward outputs and
+    // peaks of as many streams as the largest split call so far, and FS0's
+    // tables [2][w][6] + [2][w + 1][6] with the zs states behind them
+    DevBuf split_y1, split_peak, split_cz;
+    // its STRICT mode: the tables, per-stream maxima [B][2][8] and scratch
+    DevBuf strict_tab, strict_bnd, strict_sc;
+    // staging for the host API
+    DevBuf d_x;      // the staged input of a plan that does not keep z
+    DevBuf d_out, d_len, d_sync, d_edge;   // one group, whole or not at all (reserve_all); d_edge:
+                                           // amr_fsk_demod_host_edges' table [max_streams][2 pad]
+  } mem;
   // keep_z (live layout with the exact path): the column pass writes the dead
   // tiles' transform to dd [B][nd * n2] instead of over z's dead columns, so
   // all of z (the band-pass output) survives F2 for the exact path; dd also
@@ -349,18 +366,13 @@ struct amr_fsk_plan {
   // lean -- dead tiles in place, a flagged stream's F1 re-run from the
   // caller's x (E1) -- so a device-entry plan holds z + C only
   // (AMR_FSK_KEEPZ=1: dd at creation, every call keeps z; =0: never)
-  double2* dd = nullptr;
   bool keep_z = false;         // the plan can keep z (dd sized); a call does when dd is allocated
+  // reservations, counted by amr_fsk_plan_scratch_bytes before the first host
+  // entry allocates them: dd's size, and d_x's (0 with keep_z)
   int64_t dd_bytes = 0;
-  int64_t staging_bytes = 0;   // d_x of the host entries (0 with keep_z)
-  int64_t u_bytes = 0;
-  uint8_t* cmp = nullptr;      // [B][bits_stride] packed compare bits (fft.h fft_bits_stride)
-  uint32_t* words = nullptr;   // [B][n_words]
+  int64_t staging_bytes = 0;
   // the exact path for streams with a compare inside F2's margin (fsk_exact_kernels.hip)
   bool exact_on = false;
-  uint32_t* xflags = nullptr;  // [B / 32] F2's flags, bit s of word s / 32 (cleared by F1 every batch)
-  double* amb = nullptr;       // [B] F1's ambiguity scale per stream
-  int32_t* xlist = nullptr;    // [B] flagged ordinal -> stream, then [1] the count
   int32_t* xcount_host = nullptr;   // host-mapped: the count E3 last saw (FskExact count_hint)
   int32_t* xcount_dev = nullptr;    // its device pointer
   // AMR_FSK_XSTREAM=1 (an A/B, off by default): E0-E3 on a stream of their
@@ -387,17 +399,12 @@ struct amr_fsk_plan {
   static constexpr int kHintDepth = 8;
   int32_t hint_hist[kHintDepth]{};
   int hint_pos = 0;
-  double* xslots = nullptr;    // [n_slots][slot_doubles] envelope scratch
-  uint8_t* xbits = nullptr;    // [B][bits_stride] the flagged streams' exact compare bits
-  double* xpool = nullptr;     // pocketfft's twiddle / chirp tables of length n
-  PfLen* xL = nullptr;         // pocketfft's plans of length n (device copy)
   bool x_lean = false;         // pf_hilbert_lean: E2 runs the lean fused kernel
   int64_t slot_doubles = 0;
   int n_slots = 0;
   bool ran_exact = false;      // the last call ran the exact path (its count is in xlist[max_streams])
   int exact_mode = 1;          // amr_fsk_plan_set_exact_mode: 0 off, 1 F2's flags, 2 every stream
   bool no_bound = false;       // fsk_fft_bound found no tau (p.tau = +inf): mode 1 runs as mode 2
-  int64_t scratch_bytes = 0;
   // the time-split F1 (fsk_kernels.hip FS1-FS3): designed
   // with the plan; used for calls of at most kFskSplitMaxStreams streams
   // (amr_fsk_plan_set_layout overrides); its forward outputs and peaks in
@@ -409,34 +416,18 @@ struct amr_fsk_plan {
   bool split_now = false;      // this call runs the split F1 (z approximate: no keep_z, E1 re-runs F1)
   bool last_split = false;
   int64_t split_L = 0;
-  double* split_y1 = nullptr;
-  unsigned long long* split_peak = nullptr;
-  int64_t split_cap = 0;       // streams split_y1 / split_peak hold
-  int64_t split_alloc = 0;     // their bytes (not in scratch_bytes)
   int64_t split_reserved = 0;  // what amr_fsk_plan_bytes_estimate counts for them (<= 1024 streams)
   // FS0's convolution start states: tables [2][w][6] + [2][w + 1][6] (host
   // copy made with the design), on the device with the zs states in split_cz
   std::vector<double> split_tab_host;
-  double* split_cz = nullptr;
-  int64_t split_cz_bytes = 0;
   // the split F1's STRICT mode (round 6; split_strict.h strict_design_bp per
   // tone, fsk_kernels.hip FS0-FS2 with ST, KF1-KF2, FS3): designed on the
   // first strict call; its tables, per-stream maxima and scratch in
-  // strict_tab / strict_bnd / strict_sc (strict_bytes, not in split_alloc)
+  // strict_tab / strict_bnd / strict_sc
   int strict_mode = -1;        // amr_fsk_plan_set_split_strict: 1 on, 0 off, -1 the default
   bool strict_designed = false, strict_ok = false, last_strict = false;
   StrictDesign sdes[2];
-  double* strict_tab = nullptr;
-  unsigned long long* strict_bnd = nullptr;
-  double* strict_sc = nullptr;
-  int64_t strict_tab_n = 0, strict_bnd_cap = 0, strict_sc_bytes = 0, strict_bytes = 0;
   GatherGate gate;             // an all-gather still reading this plan's outputs
-  // staging for the host API
-  void* d_x = nullptr;
-  uint8_t* d_out = nullptr;
-  int64_t* d_len = nullptr;
-  int64_t* d_sync = nullptr;
-  double* d_edge = nullptr;    // amr_fsk_demod_host_edges' table [max_streams][2 pad] (with d_out)
   // timing
   bool timing = false;
   hipEvent_t ev[AMR_TF_COUNT][2]{};
@@ -445,23 +436,36 @@ struct amr_fsk_plan {
 
 namespace {
 
+// the byte totals amr_fsk_plan_scratch_bytes / amr_fsk_plan_resident_bytes report, from the buffers
+int64_t fsk_scratch_bytes(const amr_fsk_plan* pl) {      // what amr_fsk_plan_create allocated, and dd once it exists
+  const amr_fsk_plan::Mem& m = pl->mem;
+  return m.z.bytes() + m.u.bytes() + m.v.bytes() + m.dd.bytes() + m.cmp.bytes() + m.words.bytes() + m.xflags.bytes() +
+         m.amb.bytes() + m.xlist.bytes() + m.xslots.bytes() + m.xbits.bytes() + m.xpool.bytes() + m.xL.bytes() +
+         pl->fft.mem.s1.bytes() + pl->fft.mem.s2.bytes();
+}
+int64_t fsk_split_bytes(const amr_fsk_plan* pl) {
+  return pl->mem.split_y1.bytes() + pl->mem.split_peak.bytes() + pl->mem.split_cz.bytes();
+}
+int64_t fsk_strict_bytes(const amr_fsk_plan* pl) {
+  return pl->mem.strict_tab.bytes() + pl->mem.strict_bnd.bytes() + pl->mem.strict_sc.bytes();
+}
+int64_t fsk_out_staging_bytes(const amr_fsk_plan* pl) {
+  return pl->mem.d_out.bytes() + pl->mem.d_len.bytes() + pl->mem.d_sync.bytes() + pl->mem.d_edge.bytes();
+}
+
+// set device, drain both streams, drop the gather gate; then the buffers; then events and the streams
 void fsk_plan_free(amr_fsk_plan* pl) {
   if (!pl) return;
   (void)hipSetDevice(pl->device);
   if (pl->stream) (void)hipStreamSynchronize(pl->stream);
+  if (pl->xstream) (void)hipStreamSynchronize(pl->xstream);
   gate_free(pl->gate);
   if (pl->xcount_host) (void)hipHostFree(pl->xcount_host);
-  for (void* p : {(void*)pl->z, (void*)pl->u, (void*)pl->v, (void*)pl->dd, (void*)pl->cmp, (void*)pl->words, pl->d_x,
-                  (void*)pl->d_out, (void*)pl->d_len, (void*)pl->d_sync, (void*)pl->xflags, (void*)pl->amb,
-                  (void*)pl->xlist, (void*)pl->xslots, (void*)pl->xbits, (void*)pl->xpool, (void*)pl->xL,
-                  (void*)pl->split_y1, (void*)pl->split_peak, (void*)pl->split_cz, (void*)pl->d_edge,
-                  (void*)pl->strict_tab, (void*)pl->strict_bnd, (void*)pl->strict_sc})
-    if (p) (void)hipFree(p);
-  fft_plan_free(pl->fft);
+  pl->mem = amr_fsk_plan::Mem{};                 // frees every device buffer
+  pl->fft.mem = FftPlan::Mem{};
   for (auto& e : pl->ev)
     for (auto& h : e)
       if (h) (void)hipEventDestroy(h);
-  if (pl->xstream) (void)hipStreamSynchronize(pl->xstream);
   if (pl->ev_f2) (void)hipEventDestroy(pl->ev_f2);
   if (pl->ev_x) (void)hipEventDestroy(pl->ev_x);
   if (pl->xstream) (void)hipStreamDestroy(pl->xstream);
@@ -471,7 +475,7 @@ void fsk_plan_free(amr_fsk_plan* pl) {
 
 // this call keeps z whole through F2 (dd allocated: see amr_fsk_plan::dd;
 // a split call's z is not scipy's, so the exact path re-runs F1 instead)
-bool keeps_z(const amr_fsk_plan* pl) { return pl->keep_z && pl->dd != nullptr && !pl->split_now; }
+bool keeps_z(const amr_fsk_plan* pl) { return pl->keep_z && pl->mem.dd && !pl->split_now; }
 
 hipError_t mark_fsk(amr_fsk_plan* pl, int slot, int which, hipStream_t st = nullptr) {
   if (!pl->timing) return hipSuccess;
@@ -526,8 +530,8 @@ FskSplit fsk_split_params(amr_fsk_plan* pl, int64_t B, int64_t L) {
     sp.L = (sp.L + kStrictBlk - 1) / kStrictBlk * kStrictBlk;
   sp.c = (m1 + sp.L - 1) / sp.L;
   sp.tau = pl->split_tau;
-  sp.y1 = pl->split_y1;
-  sp.peak = pl->split_peak;
+  sp.y1 = pl->mem.split_y1.as<double>();
+  sp.peak = pl->mem.split_peak.as<unsigned long long>();
   pl->split_L = sp.L;
   return sp;
 }
@@ -557,10 +561,8 @@ int fsk_strict_prepare(amr_fsk_plan* pl) {
   if (!ok) return AMR_OK;
   std::vector<double> tab;
   for (int t = 0; t < 2; ++t) strict_bp_append(pl->sdes[t], tab);
-  HIP_TRY(hipMalloc((void**)&pl->strict_tab, tab.size() * 8));
-  HIP_TRY(hipMemcpy(pl->strict_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-  pl->strict_tab_n = (int64_t)tab.size();
-  pl->strict_bytes += (int64_t)tab.size() * 8;
+  HIP_TRY(pl->mem.strict_tab.reserve((int64_t)tab.size() * 8, nullptr));
+  HIP_TRY(hipMemcpy(pl->mem.strict_tab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
   pl->strict_ok = true;
   return AMR_OK;
 }
@@ -572,75 +574,36 @@ int ensure_fsk_strict(amr_fsk_plan* pl, FskSplit& sp, int64_t B) {
   sp.rows.nb1 = (m1 + kStrictBlk - 1) / kStrictBlk;
   sp.rows.c = sp.c;
   sp.rows.sstride = strict_off_end(sp.rows);
-  const int64_t need = B * 2 * sp.rows.sstride * 8;
-  if (pl->strict_sc_bytes < need || !pl->strict_sc) {
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    if (pl->strict_sc) (void)hipFree(pl->strict_sc);
-    pl->strict_bytes -= pl->strict_sc_bytes;
-    pl->strict_sc = nullptr;
-    pl->strict_sc_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&pl->strict_sc, (size_t)need));
-    pl->strict_sc_bytes = need;
-    pl->strict_bytes += need;
-  }
-  if (pl->strict_bnd_cap < B || !pl->strict_bnd) {
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    if (pl->strict_bnd) (void)hipFree(pl->strict_bnd);
-    pl->strict_bytes -= pl->strict_bnd_cap * 2 * 64;
-    pl->strict_bnd = nullptr;
-    pl->strict_bnd_cap = 0;
-    HIP_TRY(hipMalloc((void**)&pl->strict_bnd, (size_t)(B * 2 * 64)));
-    pl->strict_bnd_cap = B;
-    pl->strict_bytes += B * 2 * 64;
-  }
+  HIP_TRY(pl->mem.strict_sc.reserve(B * 2 * sp.rows.sstride * 8, pl->stream));
+  HIP_TRY(pl->mem.strict_bnd.reserve(B * 2 * 64, pl->stream));
   sp.strict = 1;
   sp.hl1 = pl->split_hl1;
-  sp.rows.sc = pl->strict_sc;
-  sp.bnd = pl->strict_bnd;
-  sp.sb[0] = strict_bp_view(pl->sdes[0], pl->strict_tab);
-  sp.sb[1] = strict_bp_view(pl->sdes[1], pl->strict_tab + strict_bp_doubles(pl->sdes[0]));
+  sp.rows.sc = pl->mem.strict_sc.as<double>();
+  sp.bnd = pl->mem.strict_bnd.as<unsigned long long>();
+  sp.sb[0] = strict_bp_view(pl->sdes[0], pl->mem.strict_tab.as<double>());
+  sp.sb[1] = strict_bp_view(pl->sdes[1], pl->mem.strict_tab.as<double>() + strict_bp_doubles(pl->sdes[0]));
   return AMR_OK;
 }
-// the tables and this call's zs in split_cz (grown as needed; counted in
-// split_alloc), then sp's pointers into it
+// the tables and this call's zs in split_cz (grown as needed), then sp's pointers into it
 int ensure_split_conv(amr_fsk_plan* pl, FskSplit& sp, int64_t B) {
   if (!sp.conv) return AMR_OK;
   const int64_t tab = (int64_t)pl->split_tab_host.size() * 8;
   const int64_t need = tab + B * 2 * sp.c * 6 * 8;
-  if (pl->split_cz_bytes < need || !pl->split_cz) {
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    if (pl->split_cz) {
-      (void)hipFree(pl->split_cz);
-      pl->split_alloc -= pl->split_cz_bytes;
-    }
-    pl->split_cz = nullptr;
-    pl->split_cz_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&pl->split_cz, (size_t)need));
-    HIP_TRY(hipMemcpy(pl->split_cz, pl->split_tab_host.data(), (size_t)tab, hipMemcpyHostToDevice));
-    pl->split_cz_bytes = need;
-    pl->split_alloc += need;
+  DevBuf& cz = pl->mem.split_cz;
+  if (cz.bytes() < need || !cz) {
+    HIP_TRY(cz.reserve(need, pl->stream));
+    HIP_TRY(hipMemcpy(cz.get(), pl->split_tab_host.data(), (size_t)tab, hipMemcpyHostToDevice));
   }
-  sp.ktab = pl->split_cz;
-  sp.z0tab = pl->split_cz + 2 * sp.w * 6;
-  sp.zs = pl->split_cz + tab / 8;
+  sp.ktab = cz.as<double>();
+  sp.z0tab = cz.as<double>() + 2 * sp.w * 6;
+  sp.zs = cz.as<double>() + tab / 8;
   return AMR_OK;
 }
+// the forward outputs and peaks of B streams
 int ensure_split_buffers(amr_fsk_plan* pl, int64_t B) {
-  if (B <= pl->split_cap) return AMR_OK;
   const int64_t m1 = pl->p.n + 2 * (int64_t)pl->p.pad;
-  if (pl->split_y1 || pl->split_peak) {
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    (void)hipFree(pl->split_y1);
-    (void)hipFree(pl->split_peak);
-    pl->split_y1 = nullptr;
-    pl->split_peak = nullptr;
-    pl->split_alloc = pl->split_cz_bytes;
-    pl->split_cap = 0;
-  }
-  HIP_TRY(hipMalloc(&pl->split_y1, (size_t)(B * 2 * m1 * 8)));
-  HIP_TRY(hipMalloc(&pl->split_peak, (size_t)(B * 8)));
-  pl->split_cap = B;
-  pl->split_alloc = B * (2 * m1 * 8 + 8) + pl->split_cz_bytes;
+  HIP_TRY(pl->mem.split_y1.reserve(B * 2 * m1 * 8, pl->stream));
+  HIP_TRY(pl->mem.split_peak.reserve(B * 8, pl->stream));
   return AMR_OK;
 }
 // does this call run the split F1?  Only with the exact path on (it is what
@@ -664,10 +627,10 @@ int run_fsk_f1(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t 
     if (int rc = ensure_split_conv(pl, sp, B)) return rc;
     if (int rc = ensure_fsk_strict(pl, sp, B)) return rc;
     pl->last_strict = sp.strict != 0;
-    HIP_TRY(launch_fsk_split(dtype, d_x, x_stride, B, pl->z, p, pl->f, sp, pl->stream));
+    HIP_TRY(launch_fsk_split(dtype, d_x, x_stride, B, pl->mem.z.as<double2>(), p, pl->f, sp, pl->stream));
     return AMR_OK;
   }
-  HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, reinterpret_cast<double*>(pl->u), pl->z, p, pl->f,
+  HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, pl->mem.u.as<double>(), pl->mem.z.as<double2>(), p, pl->f,
                               pl->stream));
   return AMR_OK;
 }
@@ -679,12 +642,12 @@ int run_fsk_f1(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t 
 int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
   FftEpi env{};
   env.mode = env_out ? kEnvOut : kEnvelope;
-  env.z = pl->z;
-  env.bits = pl->cmp;
+  env.z = pl->mem.z.as<double2>();
+  env.bits = pl->mem.cmp.as<uint8_t>();
   env.bits_stride = pl->p.bits_stride;
   if (!env_out && pl->exact_on && pl->exact_mode != 0) {
-    env.amb = pl->amb;
-    env.xflags = pl->xflags;
+    env.amb = pl->mem.amb.as<double>();
+    env.xflags = pl->mem.xflags.as<uint32_t>();
   }
   // one timing slot for the whole Hilbert filter (column, middle and final passes)
   HIP_TRY(mark_fsk(pl, AMR_TF_HILBERT, 0));
@@ -707,12 +670,14 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
       e.bits = env.bits + b0 * env.bits_stride;
       if (e.amb) e.amb += b0;
       if (e.xflags) e.xflags += b0 / 32;
-      HIP_TRY(launch_fft_hilbert_live(pl->z + b0 * pl->p.n, pl->u + b0 * (int64_t)lc.nl * lc.n2,
-                                      keeps_z(pl) ? pl->dd + b0 * (int64_t)lc.nd * lc.n2 : nullptr, pl->fft.d, nb, lc,
-                                      e, pl->stream));
+      double2* const dd = keeps_z(pl) ? pl->mem.dd.as<double2>() + b0 * (int64_t)lc.nd * lc.n2 : nullptr;
+      HIP_TRY(launch_fft_hilbert_live(pl->mem.z.as<double2>() + b0 * pl->p.n,
+                                      pl->mem.u.as<double2>() + b0 * (int64_t)lc.nl * lc.n2, dd, pl->fft.d, nb, lc, e,
+                                      pl->stream));
     }
   } else {
-    HIP_TRY(fft_hilbert(pl->fft, pl->z, pl->u, pl->v, B, env, pl->stream));
+    HIP_TRY(fft_hilbert(pl->fft, pl->mem.z.as<double2>(), pl->mem.u.as<double2>(), pl->mem.v.as<double2>(), B, env,
+                        pl->stream));
   }
   HIP_TRY(mark_fsk(pl, AMR_TF_HILBERT, 1));
   return AMR_OK;
@@ -734,19 +699,19 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
   const int launch = exact_launch_mode();
   if (launch == 0) return AMR_OK;
   FskExact X{};
-  X.flags = pl->xflags;
-  X.list = pl->xlist;
-  X.count = pl->xlist + pl->max_streams;
-  X.rows = reinterpret_cast<double*>(pl->z);
+  X.flags = pl->mem.xflags.as<uint32_t>();
+  X.list = pl->mem.xlist.as<int32_t>();
+  X.count = pl->mem.xlist.as<int32_t>() + pl->max_streams;
+  X.rows = reinterpret_cast<double*>(pl->mem.z.as<double2>());
   X.live = keeps_z(pl) ? 1 : 0;
   X.lc = pl->p.lc;
-  X.slots = pl->xslots;
+  X.slots = pl->mem.xslots.as<double>();
   X.slot_doubles = pl->slot_doubles;
   X.n_slots = pl->n_slots;
-  X.L = pl->xL;
-  X.pool = pl->xpool;
+  X.L = pl->mem.xL.as<PfLen>();
+  X.pool = pl->mem.xpool.as<double>();
   X.fct = (double)(1.0L / (long double)pl->p.n);
-  X.xbits = pl->xbits;
+  X.xbits = pl->mem.xbits.as<uint8_t>();
   X.fuse = (int)pf_fuse_on();
   X.lean = X.fuse && pl->x_lean;
   static const int xcd_pair = [] { const char* e = std::getenv("AMR_FSK_XCDPAIR"); return !(e && e[0] == '0'); }();
@@ -792,7 +757,7 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
     p1.lc = LiveCols{};
     p1.xlist = X.list;
     p1.xcount = X.count;
-    HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, reinterpret_cast<double*>(pl->u), pl->z, p1, pl->f, st));
+    HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, pl->mem.u.as<double>(), pl->mem.z.as<double2>(), p1, pl->f, st));
   }
   HIP_TRY(launch_fsk_exact_env(B, pl->p, X, st, launch != 2));
   HIP_TRY(mark_fsk(pl, AMR_TF_EXACT, 1, st));
@@ -839,9 +804,10 @@ int run_fsk_back(amr_fsk_plan* pl, int64_t B, uint8_t* d_out, int64_t out_stride
   // the diagnostic launch modes leave xbits unwritten)
   FskParams p = pl->p;
   if (!pl->ran_exact || exact_launch_mode() != 1) p.xflags = nullptr;
-  HIP_TRY(launch_fsk_decide(pl->cmp, pl->words, B, p, st));
+  HIP_TRY(launch_fsk_decide(pl->mem.cmp.as<uint8_t>(), pl->mem.words.as<uint32_t>(), B, p, st));
   HIP_TRY(gate_wait(pl->gate, st));             // the outputs: after any gather still reading them
-  HIP_TRY(launch_sync_pack(pl->words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+  HIP_TRY(launch_sync_pack(pl->mem.words.as<uint32_t>(), pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync,
+                           st));
   HIP_TRY(mark_fsk(pl, AMR_TF_DECIDE, 1));
   return AMR_OK;
 }
@@ -878,16 +844,9 @@ int run_fsk(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
 // sample): dd with keep_z (the column pass overwrites it after F1 read it),
 // else d_x, where it stays for the exact path's F1 re-run after F2.
 int staging_buffer(amr_fsk_plan* pl, void** buf) {
-  if (pl->keep_z) {
-    if (!pl->dd) {
-      HIP_TRY(hipMalloc(&pl->dd, (size_t)pl->dd_bytes));
-      pl->scratch_bytes += pl->dd_bytes;
-    }
-    *buf = pl->dd;
-    return AMR_OK;
-  }
-  if (!pl->d_x) HIP_TRY(hipMalloc(&pl->d_x, (size_t)(pl->max_streams * pl->p.n * 8)));
-  *buf = pl->d_x;
+  DevBuf& b = pl->keep_z ? pl->mem.dd : pl->mem.d_x;
+  HIP_TRY(b.reserve(pl->keep_z ? pl->dd_bytes : pl->max_streams * pl->p.n * 8, pl->stream));
+  *buf = b.get();
   return AMR_OK;
 }
 int stage_input(amr_fsk_plan* pl, const void* x, int dtype, int64_t B, int64_t x_stride, void** staged) {
@@ -899,11 +858,11 @@ int stage_input(amr_fsk_plan* pl, const void* x, int dtype, int64_t B, int64_t x
 
 // the host entries' output staging and the edge table (amr_fsk_demod_host_edges)
 int ensure_out_staging(amr_fsk_plan* pl) {
-  if (pl->d_out) return AMR_OK;
-  HIP_TRY(hipMalloc(&pl->d_out, (size_t)(pl->max_streams * pl->out_cap)));
-  HIP_TRY(hipMalloc(&pl->d_len, (size_t)pl->max_streams * 8));
-  HIP_TRY(hipMalloc(&pl->d_sync, (size_t)pl->max_streams * 8));
-  HIP_TRY(hipMalloc((void**)&pl->d_edge, (size_t)(pl->max_streams * 2 * (int64_t)pl->p.pad * 8)));
+  const int64_t ms = pl->max_streams;
+  amr_fsk_plan::Mem& m = pl->mem;
+  // (the inner parentheses keep the braces' commas from splitting the macro's argument)
+  HIP_TRY((reserve_all({{m.d_out, ms * pl->out_cap}, {m.d_len, ms * 8}, {m.d_sync, ms * 8},
+                        {m.d_edge, ms * 2 * (int64_t)pl->p.pad * 8}}, pl->stream)));
   return AMR_OK;
 }
 
@@ -1302,35 +1261,24 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
     fsk_plan_free(pl);
     return rc;
   }
-  if (pl->fft.six) pl->scratch_bytes += geo.six;
-  pl->u_bytes = geo.u;
   pl->staging_bytes = geo.staging;
   pl->dd_bytes = geo.dd;
   pl->split_reserved = geo.split;
-  struct A { void** ptr; int64_t bytes; };
+  amr_fsk_plan::Mem& m = pl->mem;
+  struct A { DevBuf& buf; int64_t bytes; };
   const A allocs[] = {
-      {(void**)&pl->z, geo.z},
-      {(void**)&pl->u, geo.u},
-      {(void**)&pl->v, geo.v},
-      {(void**)&pl->dd, geo.dd_eager ? geo.dd : 0},
-      {(void**)&pl->cmp, geo.cmp},
-      {(void**)&pl->words, geo.words},
-      {(void**)&pl->xflags, geo.xflags},
-      {(void**)&pl->amb, geo.amb},
-      {(void**)&pl->xlist, geo.xlist},
-      {(void**)&pl->xslots, geo.xslots},
-      {(void**)&pl->xbits, geo.xbits},
-      {(void**)&pl->xpool, geo.xpool},
-      {(void**)&pl->xL, geo.xplan},
+      {m.z, geo.z},         {m.u, geo.u},         {m.v, geo.v},         {m.dd, geo.dd_eager ? geo.dd : 0},
+      {m.cmp, geo.cmp},     {m.words, geo.words}, {m.xflags, geo.xflags}, {m.amb, geo.amb},
+      {m.xlist, geo.xlist}, {m.xslots, geo.xslots}, {m.xbits, geo.xbits}, {m.xpool, geo.xpool},
+      {m.xL, geo.xplan},
   };
   for (const A& a : allocs) {
     if (a.bytes == 0) continue;
-    e = hipMalloc(a.ptr, (size_t)a.bytes);
+    e = a.buf.reserve(a.bytes, nullptr);
     if (e != hipSuccess) {
       fsk_plan_free(pl);
       return fail(AMR_E_NOMEM, "hipMalloc(" + std::to_string(a.bytes) + " B): " + hipGetErrorString(e));
     }
-    pl->scratch_bytes += a.bytes;
   }
   if (geo.exact) {
     // E2's grid hint (FskExact count_hint): none yet, so the full grid
@@ -1352,10 +1300,10 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
       fsk_plan_free(pl);
       return fail(AMR_E_INVALID, "exact path: pocketfft plan of length " + std::to_string(n));
     }
-    e = hipMemcpy(pl->xpool, pool.data(), pool.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pl->xL, &L, sizeof(PfLen), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pf_finish(L, pl->xL, pl->xpool, pl->xslots, pl->stream);
-    if (e == hipSuccess) e = hipMemset(pl->xflags, 0, (size_t)geo.xflags);
+    e = hipMemcpy(pl->mem.xpool.as<double>(), pool.data(), pool.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(pl->mem.xL.as<PfLen>(), &L, sizeof(PfLen), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = pf_finish(L, m.xL.as<PfLen>(), m.xpool.as<double>(), m.xslots.as<double>(), pl->stream);
+    if (e == hipSuccess) e = hipMemset(pl->mem.xflags.as<uint32_t>(), 0, (size_t)geo.xflags);
     if (e != hipSuccess) {
       fsk_plan_free(pl);
       return fail(AMR_E_HIP, std::string("exact path tables: ") + hipGetErrorString(e));
@@ -1369,9 +1317,9 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
       fsk_plan_free(pl);
       return fail(AMR_E_INVALID, "exact path: live-layout length " + std::to_string(n) + " without a lean plan");
     }
-    pl->p.amb = pl->amb;
-    pl->p.xflags = pl->xflags;         // F3 reads a flagged stream's bits from xbits
-    pl->p.xbits = pl->xbits;
+    pl->p.amb = pl->mem.amb.as<double>();
+    pl->p.xflags = pl->mem.xflags.as<uint32_t>();         // F3 reads a flagged stream's bits from xbits
+    pl->p.xbits = pl->mem.xbits.as<uint8_t>();
     pl->n_slots = geo.n_slots;
     pl->slot_doubles = geo.slot_doubles;
     static const bool xstream_on = [] { const char* e = std::getenv("AMR_FSK_XSTREAM"); return e && e[0] == '1'; }();
@@ -1431,17 +1379,17 @@ int64_t amr_fsk_plan_scratch_bytes(const amr_fsk_plan* plan) {
   if (!plan) return -1;
   // scratch + the host-API staging (allocated on the first amr_fsk_demod_host:
   // d_x, or dd on a plan that keeps z)
-  return plan->scratch_bytes + plan->staging_bytes + (plan->dd ? 0 : plan->dd_bytes) +
+  return fsk_scratch_bytes(plan) + plan->staging_bytes + (plan->mem.dd ? 0 : plan->dd_bytes) +
          plan->max_streams * (plan->out_cap + 16 + 2 * (int64_t)plan->p.pad * 8) +
-         std::max(plan->split_reserved, plan->split_alloc + plan->strict_bytes);   // == fsk_geometry().total() (split calls <= 1024 streams)
+         // == fsk_geometry().total() (split calls <= 1024 streams)
+         std::max(plan->split_reserved, fsk_split_bytes(plan) + fsk_strict_bytes(plan));
 }
 int64_t amr_fsk_plan_resident_bytes(const amr_fsk_plan* plan) {
   if (!plan) return -1;
   // what is allocated now: a plan that only ever ran the device entry holds
   // no staging (no d_x, no dd, no output staging)
-  return plan->scratch_bytes + (plan->d_x ? plan->staging_bytes : 0) +
-         (plan->d_out ? plan->max_streams * (plan->out_cap + 16 + 2 * (int64_t)plan->p.pad * 8) : 0) +
-         plan->split_alloc + plan->strict_bytes;
+  return fsk_scratch_bytes(plan) + plan->mem.d_x.bytes() + fsk_out_staging_bytes(plan) + fsk_split_bytes(plan) +
+         fsk_strict_bytes(plan);
 }
 int64_t amr_fsk_plan_fft_length(const amr_fsk_plan* plan) { return plan ? plan->fft.M : -1; }
 int amr_fsk_plan_live_columns(const amr_fsk_plan* plan) { return plan ? plan->p.lc.on : -1; }
@@ -1553,8 +1501,8 @@ int amr_fsk_split_bounds_host(amr_fsk_plan* plan, const void* x, int dtype, int6
   if (!rc && !sp.strict) rc = fail(AMR_E_INVALID, "no strict bound for this call's chunk (not a multiple of 16)");
   plan->strict_mode = saved;
   if (rc) return rc;
-  HIP_TRY(launch_fsk_split(dtype, xs, n, B, plan->z, p, plan->f, sp, plan->stream));
-  HIP_TRY(hipMemcpyAsync(z_out, plan->z, (size_t)(B * n * 16), hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(launch_fsk_split(dtype, xs, n, B, plan->mem.z.as<double2>(), p, plan->f, sp, plan->stream));
+  HIP_TRY(hipMemcpyAsync(z_out, plan->mem.z.as<double2>(), (size_t)(B * n * 16), hipMemcpyDeviceToHost, plan->stream));
   std::vector<unsigned long long> hb((size_t)B * 16), hp((size_t)B);
   HIP_TRY(hipMemcpyAsync(hb.data(), sp.bnd, hb.size() * 8, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipMemcpyAsync(hp.data(), sp.peak, hp.size() * 8, hipMemcpyDeviceToHost, plan->stream));
@@ -1587,8 +1535,8 @@ int amr_fsk_split_bandpass_host(amr_fsk_plan* plan, const void* x, int dtype, in
   p.amb = nullptr;
   FskSplit sp = fsk_split_params(plan, B, chunk);
   if (int rc = ensure_split_conv(plan, sp, B)) return rc;
-  HIP_TRY(launch_fsk_split(dtype, xs, n, B, plan->z, p, plan->f, sp, plan->stream));
-  HIP_TRY(hipMemcpyAsync(out, plan->z, (size_t)(B * n * 16), hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(launch_fsk_split(dtype, xs, n, B, plan->mem.z.as<double2>(), p, plan->f, sp, plan->stream));
+  HIP_TRY(hipMemcpyAsync(out, plan->mem.z.as<double2>(), (size_t)(B * n * 16), hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipStreamSynchronize(plan->stream));
   return AMR_OK;
 }
@@ -1620,7 +1568,7 @@ int amr_fsk_plan_set_exact_mode(amr_fsk_plan* plan, int mode) {
   if (mode != 0 && !plan->exact_on) return fail(AMR_E_INVALID, "this plan has no exact path (no decisions, or AMR_FSK_EXACT=0)");
   plan->exact_mode = mode;
   // F3 reads a flagged stream's bits from xbits only while the exact path runs
-  plan->p.xflags = mode ? plan->xflags : nullptr;
+  plan->p.xflags = mode ? plan->mem.xflags.as<uint32_t>() : nullptr;
   return AMR_OK;
 }
 
@@ -1632,7 +1580,7 @@ int amr_fsk_plan_exact_streams(amr_fsk_plan* plan, int64_t* count) {
   *count = 0;
   if (!plan->exact_on || !plan->ran_exact) return AMR_OK;
   int32_t c = 0;
-  HIP_TRY(hipMemcpy(&c, plan->xlist + plan->max_streams, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&c, plan->mem.xlist.as<int32_t>() + plan->max_streams, 4, hipMemcpyDeviceToHost));
   *count = c;
   return AMR_OK;
 }
@@ -1693,28 +1641,29 @@ int fsk_demod_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int6
   if (B == 0) return AMR_OK;
   const int64_t cap = plan->out_cap;
   if (int rc = ensure_out_staging(plan)) return rc;
+  uint8_t* const d_out = plan->mem.d_out.as<uint8_t>();
+  int64_t *const d_len = plan->mem.d_len.as<int64_t>(), *const d_sync = plan->mem.d_sync.as<int64_t>();
   for (bool& u : plan->ev_used) u = false;
   if (plan->p.n_bits == 0) {
-    if (int rc = fsk_empty_outputs(plan, B, plan->d_len, plan->d_sync)) return rc;
+    if (int rc = fsk_empty_outputs(plan, B, d_len, d_sync)) return rc;
   } else {
     void* xs = nullptr;
     if (int rc = stage_input(plan, x, dtype, B, x_stride, &xs)) return rc;
     const double* d_edge = nullptr;
     if (edges) {
-      HIP_TRY(hipMemcpyAsync(plan->d_edge, edges, (size_t)(B * 2 * (int64_t)plan->p.pad * 8), hipMemcpyHostToDevice,
-                             plan->stream));
-      d_edge = plan->d_edge;
+      d_edge = plan->mem.d_edge.as<double>();
+      HIP_TRY(hipMemcpyAsync(plan->mem.d_edge.get(), edges, (size_t)(B * 2 * (int64_t)plan->p.pad * 8),
+                             hipMemcpyHostToDevice, plan->stream));
     }
     plan->count_sync = true;                 // this call waits anyway: the exact path sized by its own count
-    const int rc = run_fsk(plan, xs, dtype, B, plan->p.n, plan->d_out, cap, plan->d_len, plan->d_sync, d_edge);
+    const int rc = run_fsk(plan, xs, dtype, B, plan->p.n, d_out, cap, d_len, d_sync, d_edge);
     plan->count_sync = false;
     if (rc) return rc;
   }
-  if (int rc = copy_batch_d2h(out, out_stride, plan->d_out, cap, out_stride < cap ? out_stride : cap, B,
-                              plan->stream))
+  if (int rc = copy_batch_d2h(out, out_stride, d_out, cap, out_stride < cap ? out_stride : cap, B, plan->stream))
     return rc;
-  HIP_TRY(hipMemcpyAsync(out_len, plan->d_len, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipMemcpyAsync(sync_idx, plan->d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(hipMemcpyAsync(out_len, d_len, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
+  HIP_TRY(hipMemcpyAsync(sync_idx, d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipStreamSynchronize(plan->stream));
   return AMR_OK;
 }
@@ -1751,10 +1700,12 @@ int amr_fsk_demod_host_async(amr_fsk_plan* plan, const void* x, int dtype, int64
   const int64_t n = plan->p.n;
   const int64_t cap = plan->out_cap;
   if (int rc = ensure_out_staging(plan)) return rc;
+  uint8_t* const d_out = plan->mem.d_out.as<uint8_t>();
+  int64_t *const d_len = plan->mem.d_len.as<int64_t>(), *const d_sync = plan->mem.d_sync.as<int64_t>();
   hipStream_t st = plan->stream;
   for (bool& u : plan->ev_used) u = false;
   if (plan->p.n_bits == 0) {
-    if (int rc = fsk_empty_outputs(plan, B, plan->d_len, plan->d_sync)) return rc;
+    if (int rc = fsk_empty_outputs(plan, B, d_len, d_sync)) return rc;
   } else {
     void* xs = nullptr;
     if (int rc = staging_buffer(plan, &xs)) return rc;
@@ -1763,15 +1714,15 @@ int amr_fsk_demod_host_async(amr_fsk_plan* plan, const void* x, int dtype, int64
     else
       HIP_TRY(hipMemcpy2DAsync(xs, (size_t)(n * es), x, (size_t)(x_stride * es), (size_t)(n * es), (size_t)B,
                                hipMemcpyHostToDevice, st));
-    if (int rc = run_fsk(plan, xs, dtype, B, n, plan->d_out, cap, plan->d_len, plan->d_sync)) return rc;
+    if (int rc = run_fsk(plan, xs, dtype, B, n, d_out, cap, d_len, d_sync)) return rc;
   }
   if (out_stride == cap)
-    HIP_TRY(hipMemcpyAsync(out, plan->d_out, (size_t)(B * cap), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)(B * cap), hipMemcpyDeviceToHost, st));
   else
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, plan->d_out, (size_t)cap, (size_t)std::min(out_stride, cap),
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, d_out, (size_t)cap, (size_t)std::min(out_stride, cap),
                              (size_t)B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_len, plan->d_len, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sync_idx, plan->d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out_len, d_len, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sync_idx, d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, st));
   return AMR_OK;
 }
 
@@ -1791,44 +1742,43 @@ int amr_fsk_envelopes_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t
     // them on temporary buffers (a diagnostic entry, tests/test_gpu_fsk.py)
     const int64_t M = plan->fft.M;
     const int64_t ub = std::max(B * M * 16, fsk_bandpass_scratch_bytes(B, n, plan->p.pad));
-    double2 *z = nullptr, *u = nullptr, *v = nullptr;
-    void* xs = nullptr;
-    hipError_t e = hipMalloc(&z, (size_t)(B * n * 16));
-    if (e == hipSuccess) e = hipMalloc(&u, (size_t)ub);
-    if (e == hipSuccess) e = hipMalloc(&v, (size_t)(B * M * 16));
-    if (e == hipSuccess) e = hipMalloc(&xs, (size_t)(B * n * 8));
-    int rc = e == hipSuccess ? copy_batch_h2d(xs, x, n * dtype_size(dtype), x_stride * dtype_size(dtype), B,
-                                              plan->stream)
-                             : fail(AMR_E_NOMEM, std::string("envelope buffers: ") + hipGetErrorString(e));
-    if (rc == AMR_OK) {
-      FskParams pn = plan->p;
-      pn.lc = LiveCols{};
-      std::swap(plan->z, z);
-      std::swap(plan->u, u);
-      std::swap(plan->v, v);
+    const auto nomem = [](hipError_t e) {
+      return fail(AMR_E_NOMEM, std::string("envelope buffers: ") + hipGetErrorString(e));
+    };
+    DevBuf z, u, v, xs;
+    HIP_TRY_ELSE(z.reserve(B * n * 16, nullptr), nomem);
+    HIP_TRY_ELSE(u.reserve(ub, nullptr), nomem);
+    HIP_TRY_ELSE(v.reserve(B * M * 16, nullptr), nomem);
+    HIP_TRY_ELSE(xs.reserve(B * n * 8, nullptr), nomem);
+    if (int rc = copy_batch_h2d(xs.get(), x, n * dtype_size(dtype), x_stride * dtype_size(dtype), B, plan->stream))
+      return rc;
+    amr_fsk_plan::Mem& m = plan->mem;
+    FskParams pn = plan->p;
+    pn.lc = LiveCols{};
+    const auto exchange = [&] {                  // the plan's z / u / v and geometry <-> the temporaries
+      m.z.swap(z);
+      m.u.swap(u);
+      m.v.swap(v);
       std::swap(plan->p, pn);
-      rc = run_fsk_front(plan, xs, dtype, B, n, true);
-      if (rc == AMR_OK) {
-        e = hipMemcpyAsync(h.data(), hilbert_out(plan->fft, plan->u, plan->v), h.size() * 8, hipMemcpyDeviceToHost,
-                           plan->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(plan->stream);
-        if (e != hipSuccess) rc = fail(AMR_E_HIP, std::string("envelopes: ") + hipGetErrorString(e));
-      }
-      std::swap(plan->z, z);
-      std::swap(plan->u, u);
-      std::swap(plan->v, v);
-      std::swap(plan->p, pn);
-    }
-    (void)hipStreamSynchronize(plan->stream);
-    for (void* q : {(void*)z, (void*)u, (void*)v, xs})
-      if (q) (void)hipFree(q);
+    };
+    exchange();
+    const int rc = run_fsk_front(plan, xs.get(), dtype, B, n, true);
+    hipError_t e = hipSuccess;
+    if (rc == AMR_OK)
+      e = hipMemcpyAsync(h.data(), hilbert_out(plan->fft, m.u.as<double2>(), m.v.as<double2>()), h.size() * 8,
+                         hipMemcpyDeviceToHost, plan->stream);
+    // the wait whatever happened: the temporaries are freed when this block ends
+    const hipError_t es = hipStreamSynchronize(plan->stream);
+    exchange();
     if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(AMR_E_HIP, std::string("envelopes: ") + hipGetErrorString(e));
   } else {
     void* xs = nullptr;
     if (int rc = stage_input(plan, x, dtype, B, x_stride, &xs)) return rc;
     if (int rc = run_fsk_front(plan, xs, dtype, B, n, true)) return rc;
-    HIP_TRY(hipMemcpyAsync(h.data(), hilbert_out(plan->fft, plan->u, plan->v), h.size() * 8, hipMemcpyDeviceToHost,
-                           plan->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), hilbert_out(plan->fft, plan->mem.u.as<double2>(), plan->mem.v.as<double2>()),
+                           h.size() * 8, hipMemcpyDeviceToHost, plan->stream));
     HIP_TRY(hipStreamSynchronize(plan->stream));
   }
   for (int64_t i = 0; i < B * n; ++i) {
@@ -1838,31 +1788,26 @@ int amr_fsk_envelopes_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t
   return AMR_OK;
 }
 
+// The one-shot entries below declare their buffers first and their stream
+// last: the StreamScope is then synchronised and destroyed before any buffer
+// is freed, on every return path.
 int amr_fft_c2c_host(const double* in, double* out, int64_t n, int64_t batch, int inverse, int device) {
   if (!in || !out || n < 1 || batch < 0) return fail(AMR_E_INVALID, "amr_fft_c2c_host: bad argument");
   if (batch == 0) return AMR_OK;
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  DevBuf x, u, v;
   FftPlan f{};
-  int rc = fft_plan_init(f, n, st, batch);
-  double2 *x = nullptr, *u = nullptr, *v = nullptr;
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMalloc(&x, (size_t)(batch * n * 16));
-    if (e == hipSuccess) e = hipMalloc(&u, (size_t)(batch * f.M * 16));
-    if (e == hipSuccess) e = hipMalloc(&v, (size_t)(batch * f.M * 16));
-    if (e == hipSuccess) e = hipMemcpyAsync(x, in, (size_t)(batch * n * 16), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = fft_c2c(f, x, u, v, x, batch, inverse != 0, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, x, (size_t)(batch * n * 16), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  for (void* p : {(void*)x, (void*)u, (void*)v})
-    if (p) (void)hipFree(p);
-  fft_plan_free(f);
-  (void)hipStreamDestroy(st);
-  if (rc) return rc;
-  HIP_TRY(e);
+  StreamScope st;
+  HIP_TRY(StreamScope::create(st));
+  if (int rc = fft_plan_init(f, n, st.get(), batch)) return rc;
+  HIP_TRY(x.reserve(batch * n * 16, nullptr));
+  HIP_TRY(u.reserve(batch * f.M * 16, nullptr));
+  HIP_TRY(v.reserve(batch * f.M * 16, nullptr));
+  HIP_TRY(hipMemcpyAsync(x.get(), in, (size_t)(batch * n * 16), hipMemcpyHostToDevice, st.get()));
+  double2* const xd = x.as<double2>();
+  HIP_TRY(fft_c2c(f, xd, u.as<double2>(), v.as<double2>(), xd, batch, inverse != 0, st.get()));
+  HIP_TRY(hipMemcpyAsync(out, x.get(), (size_t)(batch * n * 16), hipMemcpyDeviceToHost, st.get()));
+  HIP_TRY(hipStreamSynchronize(st.get()));
   return AMR_OK;
 }
 
@@ -1870,32 +1815,23 @@ int amr_hilbert_host(const double* xr, double* analytic, int64_t n, int64_t batc
   if (!xr || !analytic || n < 1 || batch < 0) return fail(AMR_E_INVALID, "amr_hilbert_host: bad argument");
   if (batch == 0) return AMR_OK;
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  DevBuf x, u, v;
   FftPlan f{};
-  int rc = fft_plan_init(f, n, st, batch);
-  double2 *x = nullptr, *u = nullptr, *v = nullptr;
-  hipError_t e = hipSuccess;
+  StreamScope st;
+  HIP_TRY(StreamScope::create(st));
+  if (int rc = fft_plan_init(f, n, st.get(), batch)) return rc;
   std::vector<double> h((size_t)(batch * n * 2), 0.0);
-  if (!rc) {
-    for (int64_t i = 0; i < batch * n; ++i) h[(size_t)(2 * i)] = xr[i];
-    e = hipMalloc(&x, (size_t)(batch * n * 16));
-    if (e == hipSuccess) e = hipMalloc(&u, (size_t)(batch * f.M * 16));
-    if (e == hipSuccess) e = hipMalloc(&v, (size_t)(batch * f.M * 16));
-    if (e == hipSuccess) e = hipMemcpyAsync(x, h.data(), h.size() * 8, hipMemcpyHostToDevice, st);
-    FftEpi store{};
-    store.mode = kStore;
-    if (e == hipSuccess) e = fft_hilbert(f, x, u, v, batch, store, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(h.data(), hilbert_out(f, u, v), h.size() * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  for (void* p : {(void*)x, (void*)u, (void*)v})
-    if (p) (void)hipFree(p);
-  fft_plan_free(f);
-  (void)hipStreamDestroy(st);
-  if (rc) return rc;
-  HIP_TRY(e);
+  for (int64_t i = 0; i < batch * n; ++i) h[(size_t)(2 * i)] = xr[i];
+  HIP_TRY(x.reserve(batch * n * 16, nullptr));
+  HIP_TRY(u.reserve(batch * f.M * 16, nullptr));
+  HIP_TRY(v.reserve(batch * f.M * 16, nullptr));
+  HIP_TRY(hipMemcpyAsync(x.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice, st.get()));
+  FftEpi store{};
+  store.mode = kStore;
+  HIP_TRY(fft_hilbert(f, x.as<double2>(), u.as<double2>(), v.as<double2>(), batch, store, st.get()));
+  HIP_TRY(hipMemcpyAsync(h.data(), hilbert_out(f, u.as<double2>(), v.as<double2>()), h.size() * 8,
+                         hipMemcpyDeviceToHost, st.get()));
+  HIP_TRY(hipStreamSynchronize(st.get()));
   for (int64_t i = 0; i < batch * n; ++i) {
     analytic[2 * i] = xr[i];
     analytic[2 * i + 1] = h[(size_t)(2 * i)];
@@ -1907,21 +1843,16 @@ int amr_hilbert_host(const double* xr, double* analytic, int64_t n, int64_t batc
 // one-shot host entries below
 struct PfDev {
   PfLen L{};
-  PfLen* dL = nullptr;
-  double* pool = nullptr;
-  ~PfDev() {
-    if (dL) (void)hipFree(dL);
-    if (pool) (void)hipFree(pool);
-  }
+  DevBuf dL, pool;
 };
 int pf_dev_init(PfDev& D, int64_t n, double* tmp, hipStream_t st) {
   std::vector<double> pool;
   if (!pf_len_build(n, D.L, pool)) return fail(AMR_E_INVALID, "no pocketfft plan for length " + std::to_string(n));
-  HIP_TRY(hipMalloc(&D.pool, pool.size() * 8 + 16));
-  HIP_TRY(hipMalloc(&D.dL, sizeof(PfLen)));
-  HIP_TRY(hipMemcpy(D.pool, pool.data(), pool.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(D.dL, &D.L, sizeof(PfLen), hipMemcpyHostToDevice));
-  HIP_TRY(pf_finish(D.L, D.dL, D.pool, tmp, st));
+  HIP_TRY(D.pool.reserve((int64_t)pool.size() * 8 + 16, nullptr));
+  HIP_TRY(D.dL.reserve(sizeof(PfLen), nullptr));
+  HIP_TRY(hipMemcpy(D.pool.get(), pool.data(), pool.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(D.dL.get(), &D.L, sizeof(PfLen), hipMemcpyHostToDevice));
+  HIP_TRY(pf_finish(D.L, D.dL.as<PfLen>(), D.pool.as<double>(), tmp, st));
   return AMR_OK;
 }
 
@@ -1929,68 +1860,62 @@ int amr_resample_host(const double* x, int64_t nx, int64_t num, int64_t batch, d
   if (!x || !y || nx < 1 || num < 1 || batch < 0) return fail(AMR_E_INVALID, "amr_resample_host: bad argument");
   if (batch == 0) return AMR_OK;
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  const auto nomem = [](hipError_t e) {
+    return fail(AMR_E_NOMEM, std::string("resample buffers: ") + hipGetErrorString(e));
+  };
+  const auto bad = [](hipError_t e) { return fail(AMR_E_HIP, std::string("resample: ") + hipGetErrorString(e)); };
   PfDev Dx, Dy;
-  double *xd = nullptr, *yd = nullptr, *slots = nullptr;
+  DevBuf xd, yd, slots;
+  StreamScope st;
+  HIP_TRY(StreamScope::create(st));
   const int n_slots = (int)std::min<int64_t>(batch, 64);
   // scratch for the slots, and for pf_finish's transform before that
   const int64_t sd = std::max(pf_scratch_doubles_n(nx), pf_scratch_doubles_n(num)) + pf_even(std::max(nx, num));
-  int rc = AMR_OK;
-  hipError_t e = hipMalloc(&slots, (size_t)(n_slots * sd * 8));
-  if (e == hipSuccess) e = hipMalloc(&xd, (size_t)(batch * nx * 8));
-  if (e == hipSuccess) e = hipMalloc(&yd, (size_t)(batch * num * 8));
-  if (e != hipSuccess) rc = fail(AMR_E_NOMEM, std::string("resample buffers: ") + hipGetErrorString(e));
-  if (rc == AMR_OK) rc = pf_dev_init(Dx, nx, slots, st);
-  if (rc == AMR_OK) rc = pf_dev_init(Dy, num, slots, st);
-  if (rc == AMR_OK) {
-    const int64_t slot = pf_resample_slot_doubles(Dx.L, Dy.L);
-    e = hipMemcpyAsync(xd, x, (size_t)(batch * nx * 8), hipMemcpyHostToDevice, st);
-    // irfft's 1/num (pocketfft: double(1 / long double num)), then numpy's y *= num / nx
-    if (e == hipSuccess)
-      e = launch_pf_resample(Dx.dL, Dx.pool, Dy.dL, Dy.pool, xd, nx, yd, num, batch, slots, slot, n_slots,
-                             (double)(1.0L / (long double)num), (double)num / (double)nx, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(y, yd, (size_t)(batch * num * 8), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(AMR_E_HIP, std::string("resample: ") + hipGetErrorString(e));
-  }
-  (void)hipStreamSynchronize(st);
-  for (void* p : {(void*)xd, (void*)yd, (void*)slots})
-    if (p) (void)hipFree(p);
-  (void)hipStreamDestroy(st);
-  return rc;
+  HIP_TRY_ELSE(slots.reserve(n_slots * sd * 8, nullptr), nomem);
+  HIP_TRY_ELSE(xd.reserve(batch * nx * 8, nullptr), nomem);
+  HIP_TRY_ELSE(yd.reserve(batch * num * 8, nullptr), nomem);
+  if (int rc = pf_dev_init(Dx, nx, slots.as<double>(), st.get())) return rc;
+  if (int rc = pf_dev_init(Dy, num, slots.as<double>(), st.get())) return rc;
+  const int64_t slot = pf_resample_slot_doubles(Dx.L, Dy.L);
+  HIP_TRY_ELSE(hipMemcpyAsync(xd.get(), x, (size_t)(batch * nx * 8), hipMemcpyHostToDevice, st.get()), bad);
+  // irfft's 1/num (pocketfft: double(1 / long double num)), then numpy's y *= num / nx
+  HIP_TRY_ELSE(launch_pf_resample(Dx.dL.as<PfLen>(), Dx.pool.as<double>(), Dy.dL.as<PfLen>(), Dy.pool.as<double>(),
+                                  xd.as<double>(), nx, yd.as<double>(), num, batch, slots.as<double>(), slot, n_slots,
+                                  (double)(1.0L / (long double)num), (double)num / (double)nx, st.get()),
+               bad);
+  HIP_TRY_ELSE(hipMemcpyAsync(y, yd.get(), (size_t)(batch * num * 8), hipMemcpyDeviceToHost, st.get()), bad);
+  HIP_TRY_ELSE(hipStreamSynchronize(st.get()), bad);
+  return AMR_OK;
 }
 
 int amr_hilbert_env_exact_host(const double* x, int64_t n, int64_t batch, double* env, int device) {
   if (!x || !env || n < 1 || batch < 0) return fail(AMR_E_INVALID, "amr_hilbert_env_exact_host: bad argument");
   if (batch == 0) return AMR_OK;
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  const auto nomem = [](hipError_t e) {
+    return fail(AMR_E_NOMEM, std::string("envelope buffers: ") + hipGetErrorString(e));
+  };
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("exact envelopes: ") + hipGetErrorString(e));
+  };
   PfDev D;
-  double *xd = nullptr, *slots = nullptr;
+  DevBuf xd, slots;
+  StreamScope st;
+  HIP_TRY(StreamScope::create(st));
   const int64_t sd = pf_even(n) + pf_scratch_doubles_n(n);   // the fused envelope keeps the spectrum in its slot
   // as the FSK exact path: up to 512 persistent workgroups within 2 GiB
   const int n_slots = (int)std::max<int64_t>(1, std::min<int64_t>({batch, 512, ((int64_t)1 << 31) / (sd * 8)}));
-  int rc = AMR_OK;
-  hipError_t e = hipMalloc(&slots, (size_t)(n_slots * sd * 8));
-  if (e == hipSuccess) e = hipMalloc(&xd, (size_t)(batch * n * 8));
-  if (e != hipSuccess) rc = fail(AMR_E_NOMEM, std::string("envelope buffers: ") + hipGetErrorString(e));
-  if (rc == AMR_OK) rc = pf_dev_init(D, n, slots, st);
-  if (rc == AMR_OK) {
-    e = hipMemcpyAsync(xd, x, (size_t)(batch * n * 8), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-      e = launch_pf_hilbert_env(D.dL, D.pool, xd, n, batch, slots, sd, n_slots, (double)(1.0L / (long double)n),
-                                pf_hilbert_lean(D.L), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(env, xd, (size_t)(batch * n * 8), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(AMR_E_HIP, std::string("exact envelopes: ") + hipGetErrorString(e));
-  }
-  (void)hipStreamSynchronize(st);
-  for (void* p : {(void*)xd, (void*)slots})
-    if (p) (void)hipFree(p);
-  (void)hipStreamDestroy(st);
-  return rc;
+  HIP_TRY_ELSE(slots.reserve(n_slots * sd * 8, nullptr), nomem);
+  HIP_TRY_ELSE(xd.reserve(batch * n * 8, nullptr), nomem);
+  if (int rc = pf_dev_init(D, n, slots.as<double>(), st.get())) return rc;
+  HIP_TRY_ELSE(hipMemcpyAsync(xd.get(), x, (size_t)(batch * n * 8), hipMemcpyHostToDevice, st.get()), bad);
+  HIP_TRY_ELSE(launch_pf_hilbert_env(D.dL.as<PfLen>(), D.pool.as<double>(), xd.as<double>(), n, batch,
+                                     slots.as<double>(), sd, n_slots, (double)(1.0L / (long double)n),
+                                     pf_hilbert_lean(D.L), st.get()),
+               bad);
+  HIP_TRY_ELSE(hipMemcpyAsync(env, xd.get(), (size_t)(batch * n * 8), hipMemcpyDeviceToHost, st.get()), bad);
+  HIP_TRY_ELSE(hipStreamSynchronize(st.get()), bad);
+  return AMR_OK;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "amr_internal.h"
 #include "api_common.h"
+#include "dev_mem.h"
 #include "hell.h"
 #include "hell_glyphs.h"
 
@@ -119,33 +120,26 @@ int amr_hell_demod_host(const void* x, int elem, int64_t n_streams, int64_t x_st
   const int64_t used = n_pix * sps;                  // the tail past the last whole pixel stays on the host
   const int64_t wb = hell_work_bytes(sps);
   const int64_t ocap = n_out > 0 ? n_out : 1;
-  void* d_x = nullptr;
-  uint8_t* d_out = nullptr;
-  int64_t* d_len = nullptr;
-  double* d_en = nullptr;
-  void* d_work = nullptr;
-  hipError_t e = hipMalloc(&d_x, (size_t)(n_streams * used * es));
-  if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)(n_streams * ocap));
-  if (e == hipSuccess) e = hipMalloc(&d_len, (size_t)n_streams * 8);
-  if (e == hipSuccess && energy) e = hipMalloc(&d_en, (size_t)(n_streams * n_pix) * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_work, (size_t)wb);
-  if (e == hipSuccess) e = memcpy_rows(d_x, used * es, x, x_stride * es, used * es, n_streams, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    rc = amr_hell_demod_device(nullptr, d_x, elem, n_streams, used, used, baud, sample_rate, d_out, ocap, d_len, d_en,
-                               d_work, wb);
-    if (rc == AMR_OK) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess && rc == AMR_OK && n_out > 0)
-    e = memcpy_rows(out, out_stride, d_out, ocap, n_out, n_streams, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == AMR_OK) e = hipMemcpy(out_len, d_len, (size_t)n_streams * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == AMR_OK && energy)
-    e = hipMemcpy(energy, d_en, (size_t)(n_streams * n_pix) * 8, hipMemcpyDeviceToHost);
-  for (void* q : {d_x, (void*)d_out, (void*)d_len, (void*)d_en, d_work})
-    if (q) (void)hipFree(q);
-  if (rc) return rc;
-  if (e != hipSuccess)
+  const auto bad = [](hipError_t e) {
     return fail(e == hipErrorOutOfMemory ? AMR_E_NOMEM : AMR_E_HIP,
                 std::string("amr_hell_demod_host: ") + hipGetErrorString(e));
+  };
+  DevBuf d_x, d_out, d_len, d_en, d_work;
+  HIP_TRY_ELSE(d_x.reserve(n_streams * used * es, nullptr), bad);
+  HIP_TRY_ELSE(d_out.reserve(n_streams * ocap, nullptr), bad);
+  HIP_TRY_ELSE(d_len.reserve(n_streams * 8, nullptr), bad);
+  if (energy) HIP_TRY_ELSE(d_en.reserve(n_streams * n_pix * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_work.reserve(wb, nullptr), bad);
+  HIP_TRY_ELSE(memcpy_rows(d_x.get(), used * es, x, x_stride * es, used * es, n_streams, hipMemcpyHostToDevice), bad);
+  rc = amr_hell_demod_device(nullptr, d_x.get(), elem, n_streams, used, used, baud, sample_rate, d_out.as<uint8_t>(),
+                             ocap, d_len.as<int64_t>(), d_en.as<double>(), d_work.get(), wb);
+  if (rc) return rc;
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  if (n_out > 0)
+    HIP_TRY_ELSE(memcpy_rows(out, out_stride, d_out.get(), ocap, n_out, n_streams, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(out_len, d_len.get(), (size_t)n_streams * 8, hipMemcpyDeviceToHost), bad);
+  if (energy)
+    HIP_TRY_ELSE(hipMemcpy(energy, d_en.get(), (size_t)(n_streams * n_pix) * 8, hipMemcpyDeviceToHost), bad);
   return AMR_OK;
 }
 

@@ -18,6 +18,7 @@
 
 #include "amr_internal.h"
 #include "api_common.h"
+#include "dev_mem.h"
 
 namespace amr {
 hipError_t launch_tx(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
@@ -149,32 +150,26 @@ int amr_modulate_host(int mode, double baud, double f0, double f1, double sample
   if (n == 0 || n_out == 0) return AMR_OK;
   const int64_t stride = maxlen > 0 ? maxlen : 1;
   const int64_t wb = work_bytes(p, n);
-  uint8_t* d_data = nullptr;
-  int64_t* d_nb = nullptr;
-  float* d_out = nullptr;
-  int16_t* d_pcm = nullptr;
-  void* d_work = nullptr;
-  hipError_t e = hipMalloc(&d_data, (size_t)(n * stride));
-  if (e == hipSuccess) e = hipMalloc(&d_nb, (size_t)n * 8);
-  if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)(n * n_out) * 4);
-  if (e == hipSuccess && pcm) e = hipMalloc(&d_pcm, (size_t)(n * n_out) * 2);
-  if (e == hipSuccess) e = hipMalloc(&d_work, (size_t)wb);
-  if (e == hipSuccess && maxlen > 0)
-    e = memcpy_rows(d_data, stride, data, data_stride, maxlen, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_nb, n_bytes, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    rc = amr_modulate_device(nullptr, mode, baud, f0, f1, sample_rate, d_data, stride, d_nb, n, d_out, n_out, n_out,
-                             d_pcm, n_out, d_work, wb);
-    if (rc == AMR_OK) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess && rc == AMR_OK)
-    e = memcpy_rows(out, out_stride * 4, d_out, n_out * 4, n_out * 4, n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == AMR_OK && pcm)
-    e = memcpy_rows(pcm, pcm_stride * 2, d_pcm, n_out * 2, n_out * 2, n, hipMemcpyDeviceToHost);
-  for (void* q : {(void*)d_data, (void*)d_nb, (void*)d_out, (void*)d_pcm, d_work})
-    if (q) (void)hipFree(q);
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("amr_modulate_host: ") + hipGetErrorString(e));
+  };
+  DevBuf d_data, d_nb, d_out, d_pcm, d_work;
+  HIP_TRY_ELSE(d_data.reserve(n * stride, nullptr), bad);
+  HIP_TRY_ELSE(d_nb.reserve(n * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_out.reserve(n * n_out * 4, nullptr), bad);
+  if (pcm) HIP_TRY_ELSE(d_pcm.reserve(n * n_out * 2, nullptr), bad);
+  HIP_TRY_ELSE(d_work.reserve(wb, nullptr), bad);
+  if (maxlen > 0)
+    HIP_TRY_ELSE(memcpy_rows(d_data.get(), stride, data, data_stride, maxlen, n, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(hipMemcpy(d_nb.get(), n_bytes, (size_t)n * 8, hipMemcpyHostToDevice), bad);
+  rc = amr_modulate_device(nullptr, mode, baud, f0, f1, sample_rate, d_data.as<uint8_t>(), stride,
+                           d_nb.as<int64_t>(), n, d_out.as<float>(), n_out, n_out, d_pcm.as<int16_t>(), n_out,
+                           d_work.get(), wb);
   if (rc) return rc;
-  if (e != hipSuccess) return fail(AMR_E_HIP, std::string("amr_modulate_host: ") + hipGetErrorString(e));
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  HIP_TRY_ELSE(memcpy_rows(out, out_stride * 4, d_out.get(), n_out * 4, n_out * 4, n, hipMemcpyDeviceToHost), bad);
+  if (pcm)
+    HIP_TRY_ELSE(memcpy_rows(pcm, pcm_stride * 2, d_pcm.get(), n_out * 2, n_out * 2, n, hipMemcpyDeviceToHost), bad);
   return AMR_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "amr_internal.h"
 #include "api_common.h"
+#include "dev_mem.h"
 #include "viterbi.h"
 
 using namespace amr;
@@ -27,18 +28,6 @@ const char* err_name(hipError_t e) { return hipGetErrorString(e); }
 int hip_fail(const char* who, hipError_t e) {
   return fail(e == hipErrorOutOfMemory ? AMR_E_NOMEM : AMR_E_HIP, std::string(who) + ": " + err_name(e));
 }
-
-struct DevBufs {                                   // frees what a host entry allocated, on every return path
-  std::vector<void*> p;
-  hipError_t alloc(void** q, int64_t bytes) {
-    const hipError_t e = hipMalloc(q, (size_t)std::max<int64_t>(bytes, 1));
-    if (e == hipSuccess) p.push_back(*q);
-    return e;
-  }
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
 
 }  // namespace
 
@@ -75,22 +64,18 @@ int amr_conv_encode_host(const uint8_t* in, int64_t in_stride, const int64_t* in
   if (n > ((int64_t)0x7fffffff * 256) / lmax)
     return fail(AMR_E_INVALID, "amr_conv_encode_host: messages x coded bytes exceeds one launch");
   const int64_t istr = std::max<int64_t>(nmax, 1);
-  DevBufs bufs;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  int64_t* d_len = nullptr;
-  hipError_t e = bufs.alloc((void**)&d_in, n * istr);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_out, n * lmax);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_len, n * 8);
-  if (e == hipSuccess && nmax > 0) e = memcpy_rows(d_in, istr, in, in_stride, nmax, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_len, in_len, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_conv_encode(d_in, istr, d_len, n, d_out, lmax, lmax, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  std::vector<uint8_t> tmp;
-  if (e == hipSuccess) {
-    tmp.resize((size_t)(n * lmax));
-    e = hipMemcpy(tmp.data(), d_out, tmp.size(), hipMemcpyDeviceToHost);
-  }
-  if (e != hipSuccess) return hip_fail("amr_conv_encode_host", e);
+  const auto bad = [](hipError_t e) { return hip_fail("amr_conv_encode_host", e); };
+  DevBuf d_in, d_out, d_len;
+  HIP_TRY_ELSE(d_in.reserve(n * istr, nullptr), bad);
+  HIP_TRY_ELSE(d_out.reserve(n * lmax, nullptr), bad);
+  HIP_TRY_ELSE(d_len.reserve(n * 8, nullptr), bad);
+  if (nmax > 0) HIP_TRY_ELSE(memcpy_rows(d_in.get(), istr, in, in_stride, nmax, n, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(hipMemcpy(d_len.get(), in_len, (size_t)n * 8, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(launch_conv_encode(d_in.as<uint8_t>(), istr, d_len.as<int64_t>(), n, d_out.as<uint8_t>(), lmax, lmax,
+                                  nullptr), bad);
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  std::vector<uint8_t> tmp((size_t)(n * lmax));
+  HIP_TRY_ELSE(hipMemcpy(tmp.data(), d_out.get(), tmp.size(), hipMemcpyDeviceToHost), bad);
   for (int64_t i = 0; i < n; ++i) {                // only the codeword's own bytes reach the caller's row
     out_len[i] = 2 * in_len[i] + 2;
     std::memcpy(out + i * out_stride, tmp.data() + i * lmax, (size_t)out_len[i]);
@@ -146,31 +131,27 @@ int amr_viterbi_decode_host(const uint8_t* in, int64_t in_stride, const int64_t*
   const int64_t per = vit_work_words(lmax) * 8;
   const int64_t chunk = std::min(n, std::max<int64_t>(1, kVitWorkBudget / per));
   const int64_t ocap = std::max<int64_t>(nmax, 1);
-  DevBufs bufs;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  int64_t *d_len = nullptr, *d_olen = nullptr;
-  int32_t* d_met = nullptr;
-  void* d_work = nullptr;
-  hipError_t e = bufs.alloc((void**)&d_in, chunk * lmax);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_out, chunk * ocap);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_len, chunk * 8);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_olen, chunk * 8);
-  if (e == hipSuccess) e = bufs.alloc((void**)&d_met, chunk * 4);
-  if (e == hipSuccess) e = bufs.alloc(&d_work, chunk * per);
-  if (e != hipSuccess) return hip_fail("amr_viterbi_decode_host", e);
+  const auto bad = [](hipError_t e) { return hip_fail("amr_viterbi_decode_host", e); };
+  DevBuf d_in, d_out, d_len, d_olen, d_met, d_work;
+  HIP_TRY_ELSE(d_in.reserve(chunk * lmax, nullptr), bad);
+  HIP_TRY_ELSE(d_out.reserve(chunk * ocap, nullptr), bad);
+  HIP_TRY_ELSE(d_len.reserve(chunk * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_olen.reserve(chunk * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_met.reserve(chunk * 4, nullptr), bad);
+  HIP_TRY_ELSE(d_work.reserve(chunk * per, nullptr), bad);
   std::vector<uint8_t> tmp((size_t)(chunk * ocap));
   for (int64_t c0 = 0; c0 < n; c0 += chunk) {
     const int64_t m = std::min(chunk, n - c0);
-    e = memcpy_rows(d_in, lmax, in + c0 * in_stride, in_stride, lmax, m, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_len, in_len + c0, (size_t)m * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail("amr_viterbi_decode_host", e);
-    const int rc = amr_viterbi_decode_device(nullptr, d_in, lmax, d_len, m, d_out, ocap, d_olen, d_met, d_work, m * per);
+    HIP_TRY_ELSE(memcpy_rows(d_in.get(), lmax, in + c0 * in_stride, in_stride, lmax, m, hipMemcpyHostToDevice), bad);
+    HIP_TRY_ELSE(hipMemcpy(d_len.get(), in_len + c0, (size_t)m * 8, hipMemcpyHostToDevice), bad);
+    const int rc = amr_viterbi_decode_device(nullptr, d_in.as<uint8_t>(), lmax, d_len.as<int64_t>(), m,
+                                             d_out.as<uint8_t>(), ocap, d_olen.as<int64_t>(), d_met.as<int32_t>(),
+                                             d_work.get(), m * per);
     if (rc) return rc;
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_len + c0, d_olen, (size_t)m * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(metric + c0, d_met, (size_t)m * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && nmax > 0) e = hipMemcpy(tmp.data(), d_out, (size_t)(m * ocap), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("amr_viterbi_decode_host", e);
+    HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+    HIP_TRY_ELSE(hipMemcpy(out_len + c0, d_olen.get(), (size_t)m * 8, hipMemcpyDeviceToHost), bad);
+    HIP_TRY_ELSE(hipMemcpy(metric + c0, d_met.get(), (size_t)m * 4, hipMemcpyDeviceToHost), bad);
+    if (nmax > 0) HIP_TRY_ELSE(hipMemcpy(tmp.data(), d_out.get(), (size_t)(m * ocap), hipMemcpyDeviceToHost), bad);
     for (int64_t i = 0; i < m; ++i)                // only the decoded bytes reach the caller's row
       if (out_len[c0 + i] > 0)
         std::memcpy(out + (c0 + i) * out_stride, tmp.data() + i * ocap, (size_t)out_len[c0 + i]);

@@ -123,3 +123,25 @@ def test_fec_encode_matches_golden(golden):
     rs = fec.ReedSolomonFEC()
     enc = rs.encode(b"hello world!")
     assert enc.hex() in [f["in"] for f in manifest["fec"]]
+
+
+def test_dev_mem_failure_paths(tmp_path):
+    """csrc/dev_mem.h's failure paths (tests/host/dev_mem_check.cpp, a
+    stand-alone program that needs no GPU): a failed reserve leaves the buffer
+    empty, a failed group reserve leaves every member as it was, moved-from
+    buffers are empty, and nothing is freed twice."""
+    import shutil
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = tmp_path / "dev_mem_check"
+    cmd = [cxx, "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+           "-I", os.path.join(os.path.dirname(here), "audio-modem-radio_amd", "csrc"),
+           os.path.join(here, "host", "dev_mem_check.cpp"), "-L", os.path.join(rocm, "lib"), "-lamdhip64",
+           "-Wl,-rpath," + os.path.join(rocm, "lib"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "dev_mem ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
