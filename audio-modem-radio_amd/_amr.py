@@ -66,6 +66,8 @@ EXPORTS = [
     "amr_hell_pixels", "amr_hell_work_bytes", "amr_hell_demod_host", "amr_hell_demod_device", "amr_hell_glyph_rows",
     "amr_conv_encoded_len", "amr_conv_encode_host", "amr_viterbi_work_bytes", "amr_viterbi_decode_device",
     "amr_viterbi_decode_host",
+    "amr_psk_demod_soft_host", "amr_psk_demod_soft_device", "amr_psk_soft_host", "amr_viterbi_soft_work_bytes",
+    "amr_viterbi_decode_soft_device", "amr_viterbi_decode_soft_host",
 ]
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL = 0, 1, 2, 3
@@ -378,6 +380,12 @@ def lib():
             "amr_viterbi_work_bytes": (I64, [I64, I64]),
             "amr_viterbi_decode_device": (I32, [P, P, I64, P, I64, P, I64, P, P, P, I64]),
             "amr_viterbi_decode_host": (I32, [P, I64, P, I64, P, I64, P, P]),
+            "amr_psk_demod_soft_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, P, I64]),
+            "amr_psk_demod_soft_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, P, I64]),
+            "amr_psk_soft_host": (I32, [I32, P, I64, I64, P]),
+            "amr_viterbi_soft_work_bytes": (I64, [I64, I64]),
+            "amr_viterbi_decode_soft_device": (I32, [P, P, I64, I64, P, I64, P, I64, P, P, P, I64]),
+            "amr_viterbi_decode_soft_host": (I32, [P, I64, I64, P, I64, P, I64, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -622,6 +630,38 @@ class PskPlan:
             outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
             syncs[s0:s0 + nb] = sy
         return outs, syncs
+
+    def _demod_soft(self, xk: np.ndarray, edges):
+        B = xk.shape[0]
+        outs, softs, syncs = [], [], np.empty(B, np.int64)
+        cap = max(self.out_cap, 1)
+        for s0 in range(0, B, self.max_streams):
+            xb = xk[s0:s0 + self.max_streams]
+            eb = None if edges is None else edges[s0:s0 + self.max_streams]
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            soft = np.empty((nb, 8 * cap), np.int8)
+            ln = np.empty(nb, np.int64)
+            sy = np.empty(nb, np.int64)
+            with self.lock:
+                check(lib().amr_psk_demod_soft_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, xb.shape[1], ptr(out),
+                                                    cap, ptr(ln), ptr(sy), None if eb is None else ptr(eb),
+                                                    ptr(soft), 8 * cap))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            softs += [soft[i, :8 * ln[i]].copy() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+        return outs, syncs, softs
+
+    def demod_soft_host(self, x: np.ndarray):
+        """demod_host with the soft values (amr_psk_demod_soft_host):
+        (list[bytes], sync, list[int8 array]); soft[i][j] belongs to bit j of
+        outs[i], so np.packbits(soft[i] > 0) is outs[i] again."""
+        return self._demod_soft(np.ascontiguousarray(x), None)
+
+    def demod_soft_host_raw(self, x: np.ndarray):
+        """demod_host_raw with the soft values."""
+        xk, edges = raw_input(np.atleast_2d(x), 3 * len(self.bp[0]))
+        return self._demod_soft(xk, edges)
 
     def scratch_bytes(self) -> int:
         """Device bytes this plan holds (scratch + host-API staging)."""
@@ -884,6 +924,51 @@ def viterbi_decode(datas):
     check(lib().amr_set_device(default_device()))
     check(lib().amr_viterbi_decode_host(ptr(buf), stride, ptr(ln), n, ptr(out), cap, ptr(out_len), ptr(metric)))
     return [out[i, :out_len[i]].tobytes() for i in range(n)], [int(v) for v in metric]
+
+
+VITERBI_SOFT_MAX_VALS = (1 << 21) - 4
+
+
+def is_soft_row_len(n: int) -> bool:
+    """A soft row length of the soft-input decoder: the bit stream, 16 k + 12
+    values, or a codeword's byte-aligned image, 16 k >= 16 values."""
+    return 12 <= n <= VITERBI_SOFT_MAX_VALS and (n % 16 == 12 or n % 16 == 0)
+
+
+def viterbi_decode_soft(softs):
+    """Batched soft-input decode of the K=7 code on the GPU
+    (amr_viterbi_decode_soft_host): softs are int8 rows (> 0 bit 1, < 0 bit 0,
+    0 an erasure).  Returns (list[bytes], list[int]): the messages and, per
+    row, the sum of |value| where it disagrees with the decoded message's codeword."""
+    require_gpu()
+    softs = [np.ascontiguousarray(s, np.int8).ravel() for s in softs]
+    n = len(softs)
+    if n == 0:
+        return [], []
+    ln = np.array([s.size for s in softs], np.int64)
+    stride = max(1, int(ln.max()))
+    buf = np.zeros((n, stride), np.int8)
+    for i, s in enumerate(softs):
+        buf[i, :s.size] = s
+    cap = max(1, stride // 16)
+    out = np.zeros((n, cap), np.uint8)
+    out_len = np.zeros(n, np.int64)
+    metric = np.zeros(n, np.int32)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_viterbi_decode_soft_host(ptr(buf), stride, 0, ptr(ln), n, ptr(out), cap, ptr(out_len), ptr(metric)))
+    return [out[i, :out_len[i]].tobytes() for i in range(n)], [int(v) for v in metric]
+
+
+def psk_soft(kind: str, sym: np.ndarray) -> np.ndarray:
+    """The soft stage alone on the GPU (K4a then K4s, amr_psk_soft_host): sym
+    [B][S] complex128 -> int8 [B][bits], one value per decided bit from bit 0."""
+    require_gpu()
+    sym = np.ascontiguousarray(np.atleast_2d(sym), np.complex128)
+    B, S = sym.shape
+    nbits = max(0, (S - 1) * (2 if kind == "qpsk" else 1))
+    soft = np.zeros((B, nbits), np.int8)
+    check(lib().amr_psk_soft_host(PSK_QPSK if kind == "qpsk" else PSK_BPSK, ptr(sym), B, S, ptr(soft)))
+    return soft
 
 
 def fft(x: np.ndarray, inverse: bool = False) -> np.ndarray:

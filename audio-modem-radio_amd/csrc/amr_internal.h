@@ -79,6 +79,9 @@ struct PskBuffers {
   // the band-pass input's odd extension as the caller's dtype formed it
   // (odd_ext.h): [B][2 * pad1] (the left pad, then the right), or null
   const double* edge;
+  // 1: the lane low-pass must leave the symbol samples in s1 and the slicing to K4a
+  // (never its fused slicer): the soft-output entries read them there (K4s)
+  int no_fuse;
 };
 
 // the time-split strict bound's block of outputs (split_strict.h, split_bound.h KB1 / KB2)

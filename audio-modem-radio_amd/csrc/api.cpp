@@ -25,6 +25,7 @@ hipError_t launch_psk_lowpass_fwd(const PskBuffers&, const PskParams&, const Iir
 hipError_t launch_psk_lowpass_bwd(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_lowpass_exact(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_slice(const PskBuffers&, const PskParams&, hipStream_t, bool only_flagged = false);
+hipError_t launch_psk_soft(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
 hipError_t launch_psk_bandpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_bandpass_fixup(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 bool psk_lane_fused(const PskBuffers&, const PskParams&);
@@ -279,6 +280,21 @@ struct amr_comm {
 };
 
 namespace {
+// the plan's layout bookkeeping (amr_psk_plan_last_*), which a soft call leaves as the hard calls set it
+struct LastCall {
+  amr_psk_plan* pl;
+  int layout, lowpass;
+  bool f32f, strict;
+  explicit LastCall(amr_psk_plan* p)
+      : pl(p), layout(p->last_layout), lowpass(p->last_lowpass), f32f(p->last_f32f), strict(p->last_strict) {}
+  ~LastCall() {
+    pl->last_layout = layout;
+    pl->last_lowpass = lowpass;
+    pl->last_f32f = f32f;
+    pl->last_strict = strict;
+  }
+};
+
 // bytes of s1 / s3 each layout needs (psk_kernels.hip / psk_lane_kernels.hip)
 int64_t lane_s1_bytes(const amr_psk_plan* pl) {
   const int64_t g = pl->groups;
@@ -428,7 +444,8 @@ double f32_design(const Iir& lp);
 int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, int64_t L,
                         double* ebound = nullptr);
 int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
-                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx);
+                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx, int8_t* soft = nullptr,
+                   int64_t soft_stride = 0);
 }  // namespace
 
 extern "C" {
@@ -1037,9 +1054,15 @@ int ensure_split_zs(amr_psk_plan* pl, const PskSplit& sp, int64_t B) {
 // Launch the whole PSK pipeline on plan->stream.  Caller holds plan->mu.
 // d_edge: the band-pass's odd-extension table [B][2 pad1] of a raw-integer
 // capture (odd_ext.h), or null
+// d_soft: non-null, the soft values too [B][soft_stride] (K4s).
+// They are defined on the reference's own symbol samples, so such a call runs
+// a layout that leaves those in s1: the row layout in place of the time-split
+// one (whose unflagged streams hold approximations), the lane layout with
+// K4a instead of its fused slicer.
 int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, uint8_t* d_out,
             int64_t out_stride, int64_t* d_len, int64_t* d_sync, uint8_t* d_fec, int64_t fec_stride,
-            int64_t* d_fec_len, int32_t* d_crc, const double* d_edge = nullptr) {
+            int64_t* d_fec_len, int32_t* d_crc, const double* d_edge = nullptr, int8_t* d_soft = nullptr,
+            int64_t soft_stride = 0) {
   if (B < 0 || B > pl->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
   if (dtype_size(dtype) == 0) return fail(AMR_E_INVALID, "unknown dtype");
   if (x_stride < pl->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
@@ -1079,6 +1102,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
   else if (live >= kLaneMinLiveStreams) layout = AMR_LAYOUT_LANE;
   else layout = split_force != 0 && live <= kSplitMaxLiveStreams ? AMR_LAYOUT_SPLIT : AMR_LAYOUT_ROW;
   if (layout == AMR_LAYOUT_LANE && !lane_ok) layout = AMR_LAYOUT_ROW;
+  if (layout == AMR_LAYOUT_SPLIT && d_soft) layout = AMR_LAYOUT_ROW;
   if (layout == AMR_LAYOUT_SPLIT) {
     if (!pl->split_designed) split_design(pl);
     if (!pl->split_ok || B > 65535 || pl->p.n_sym < 2) layout = AMR_LAYOUT_ROW;
@@ -1117,6 +1141,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
   b.out_len = d_len;
   b.sync_idx = d_sync;
   b.edge = d_edge;
+  b.no_fuse = d_soft ? 1 : 0;
   // AMR_SYNC_EACH_KERNEL=1: synchronise after every launch so a fault names its kernel
   static const bool sync_each = [] {
     const char* e = std::getenv("AMR_SYNC_EACH_KERNEL");
@@ -1212,6 +1237,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(launch_psk_slice(b, pl->p, st, sliced));   // then only the K3x streams
     HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
     HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+    if (d_soft) HIP_TRY(launch_psk_soft(b, pl->p, d_soft, soft_stride, st));
     HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
   } else {
     HIP_TRY(mark(AMR_T_BANDPASS, 0));
@@ -1235,6 +1261,7 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
     HIP_TRY(launch_psk_slice(b, pl->p, st));
     HIP_TRY(gate_wait(pl->gate, st));
     HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
+    if (d_soft) HIP_TRY(launch_psk_soft(b, pl->p, d_soft, soft_stride, st));
     HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
   }
   if (d_fec) {
@@ -1339,6 +1366,34 @@ int amr_psk_demod_host_edges(amr_psk_plan* plan, const void* x, int dtype, int64
   return psk_demod_host(plan, x, dtype, B, x_stride, edges, out, out_stride, out_len, sync_idx);
 }
 
+// ---- soft-decision output (K4s) --------------------------------
+int amr_psk_demod_soft_device(amr_psk_plan* plan, const void* d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                              uint8_t* d_out, int64_t out_stride, int64_t* d_out_len, int64_t* d_sync_idx,
+                              const double* d_edges, int8_t* d_soft, int64_t soft_stride) {
+  if (n_streams < 0 || x_stride < 0 || out_stride < 0 || soft_stride < 0)
+    return fail(AMR_E_INVALID, "amr_psk_demod_soft_device: negative argument");
+  if (!plan || (n_streams && (!d_x || !d_out || !d_out_len || !d_sync_idx || !d_soft)))
+    return fail(AMR_E_INVALID, "amr_psk_demod_soft_device: NULL argument");
+  if (soft_stride < 8 * plan->out_cap)
+    return fail(AMR_E_INVALID, "amr_psk_demod_soft_device: soft_stride < 8 * amr_psk_plan_out_capacity()");
+  std::lock_guard<std::mutex> lk(plan->mu);
+  HIP_TRY(hipSetDevice(plan->device));
+  LastCall keep(plan);
+  return run_psk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, nullptr, 0, nullptr,
+                 nullptr, d_edges, d_soft, soft_stride);
+}
+
+int amr_psk_demod_soft_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, uint8_t* out,
+                            int64_t out_stride, int64_t* out_len, int64_t* sync_idx, const double* edges,
+                            int8_t* soft, int64_t soft_stride) {
+  if (B < 0 || x_stride < 0 || out_stride < 0 || soft_stride < 0)
+    return fail(AMR_E_INVALID, "amr_psk_demod_soft_host: negative argument");
+  if (!plan || (B && !soft)) return fail(AMR_E_INVALID, "amr_psk_demod_soft_host: NULL argument");
+  if (soft_stride < 8 * plan->out_cap)
+    return fail(AMR_E_INVALID, "amr_psk_demod_soft_host: soft_stride < 8 * amr_psk_plan_out_capacity()");
+  return psk_demod_host(plan, x, dtype, B, x_stride, edges, out, out_stride, out_len, sync_idx, soft, soft_stride);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1353,8 +1408,10 @@ int psk_host_staging(amr_psk_plan* pl) {
                        pl->stream)));
   return AMR_OK;
 }
+// soft: non-null, the soft values too (amr_psk_demod_soft_host), through a staging block of this call's own
 int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
-                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
+                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx, int8_t* soft,
+                   int64_t soft_stride) {
   if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
     return fail(AMR_E_INVALID, "amr_psk_demod_host: NULL argument");
   const int64_t es = dtype_size(dtype);
@@ -1381,14 +1438,31 @@ int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int6
     HIP_TRY(hipMemcpyAsync(m.d_edge.get(), edges, (size_t)eb, hipMemcpyHostToDevice, plan->stream));
     d_edge = m.d_edge.as<double>();
   }
-  rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
-               m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge);
+  // the soft values' staging is this call's own: every row the kernel can write, 8 * out_len <= n_bits values
+  // (hipFree, when the call returns, waits for the device)
+  const int64_t sv = std::max<int64_t>(plan->p.n_bits, 1);
+  DevBuf d_soft;
+  if (soft) {
+    HIP_TRY(d_soft.reserve(B * sv, nullptr));
+    LastCall keep(plan);
+    rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
+                 m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge, d_soft.as<int8_t>(), sv);
+  } else {
+    rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
+                 m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge);
+  }
   if (rc) return rc;
   rc = copy_batch_d2h(out, out_stride, m.d_out.get(), cap, out_stride < cap ? out_stride : cap, B, plan->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_len, m.d_len.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipMemcpyAsync(sync_idx, m.d_sync.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipStreamSynchronize(plan->stream));
+  if (soft) {                                      // only the values of the stream's bytes reach the caller's row
+    std::vector<int8_t> tmp((size_t)(B * sv));
+    HIP_TRY(hipMemcpy(tmp.data(), d_soft.get(), tmp.size(), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < B; ++i)
+      std::memcpy(soft + i * soft_stride, tmp.data() + i * sv, (size_t)std::min(8 * out_len[i], soft_stride));
+  }
   return AMR_OK;
 }
 }  // namespace
@@ -1511,11 +1585,14 @@ int amr_synth_tile_noise(const float* d_base, int64_t n_base, int64_t n_samples,
   return AMR_OK;
 }
 
-// ---- the slicer stage alone (modem.py:214-241 / 100-105) ---------------------
-int amr_psk_slice_host(int kind, const double* sym, int64_t n_streams, int64_t n_sym, uint32_t* words) {
-  if (kind != AMR_PSK_QPSK && kind != AMR_PSK_BPSK) return fail(AMR_E_INVALID, "unknown PSK kind");
-  if (n_streams < 0 || n_sym < 0 || (n_streams && n_sym && (!sym || !words)))
-    return fail(AMR_E_INVALID, "amr_psk_slice_host: bad argument");
+// ---- the slicer stage alone (modem.py:214-241 / 100-105), and the soft stage behind it ----
+// K4a on given symbols: the words to `words` (or null); with `soft` K4s too, every bit from 0
+static int psk_symbol_stages(const char* who, int kind, const double* sym, int64_t n_streams, int64_t n_sym,
+                             uint32_t* words, int8_t* soft) {
+  const std::string name(who);
+  if (kind != AMR_PSK_QPSK && kind != AMR_PSK_BPSK) return fail(AMR_E_INVALID, name + ": unknown PSK kind");
+  if (n_streams < 0 || n_sym < 0 || (n_streams && n_sym && (!sym || (!words && !soft))))
+    return fail(AMR_E_INVALID, name + ": bad argument");
   PskParams p{};
   p.kind = kind;
   p.n_sym = n_sym;
@@ -1529,21 +1606,33 @@ int amr_psk_slice_host(int kind, const double* sym, int64_t n_streams, int64_t n
     for (int64_t k = 0; k < n_sym; ++k)
       for (int c = 0; c < 2; ++c)
         h[(size_t)(((s >> 6) * 2 + c) * n_sym + k) * 64 + (s & 63)] = sym[(s * n_sym + k) * 2 + c];
-  const auto bad = [](hipError_t e) {
-    return fail(AMR_E_HIP, std::string("amr_psk_slice_host: ") + hipGetErrorString(e));
-  };
-  DevBuf d_sym, d_words;
+  const auto bad = [&name](hipError_t e) { return fail(AMR_E_HIP, name + ": " + hipGetErrorString(e)); };
+  DevBuf d_sym, d_words, d_soft;
   HIP_TRY_ELSE(d_sym.reserve((int64_t)h.size() * 8, nullptr), bad);
   HIP_TRY_ELSE(d_words.reserve(n_streams * p.n_words * 4, nullptr), bad);
+  if (soft) HIP_TRY_ELSE(d_soft.reserve(n_streams * p.n_bits, nullptr), bad);
   HIP_TRY_ELSE(hipMemcpy(d_sym.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice), bad);
   PskBuffers b{};
   b.n_streams = n_streams;
   b.s1 = d_sym.as<double>();
   b.words = d_words.as<uint32_t>();
   HIP_TRY_ELSE(launch_psk_slice(b, p, nullptr), bad);
+  if (soft) HIP_TRY_ELSE(launch_psk_soft(b, p, d_soft.as<int8_t>(), p.n_bits, nullptr), bad);
   HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
-  HIP_TRY_ELSE(hipMemcpy(words, d_words.get(), (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost), bad);
+  if (words)
+    HIP_TRY_ELSE(hipMemcpy(words, d_words.get(), (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost), bad);
+  if (soft) HIP_TRY_ELSE(hipMemcpy(soft, d_soft.get(), (size_t)(n_streams * p.n_bits), hipMemcpyDeviceToHost), bad);
   return AMR_OK;
+}
+
+int amr_psk_slice_host(int kind, const double* sym, int64_t n_streams, int64_t n_sym, uint32_t* words) {
+  if (n_streams > 0 && n_sym > 0 && !words) return fail(AMR_E_INVALID, "amr_psk_slice_host: bad argument");
+  return psk_symbol_stages("amr_psk_slice_host", kind, sym, n_streams, n_sym, words, nullptr);
+}
+
+int amr_psk_soft_host(int kind, const double* sym, int64_t n_streams, int64_t n_sym, int8_t* soft) {
+  if (n_streams > 0 && n_sym > 0 && !soft) return fail(AMR_E_INVALID, "amr_psk_soft_host: bad argument");
+  return psk_symbol_stages("amr_psk_soft_host", kind, sym, n_streams, n_sym, nullptr, soft);
 }
 
 // ---- FBP frame parse (decoder.py:142-208) ------------------------------------

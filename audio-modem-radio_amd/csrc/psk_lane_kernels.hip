@@ -1517,7 +1517,7 @@ static int launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hipS
     return e ? (e[0] == '1' ? 1 : 0) : -1;
   }();
   const int64_t live = b.n_streams * (b.inflight > 1 ? b.inflight : 1);
-  const bool fuse = S_ > 0 && lane_wpb() >= 2 && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
+  const bool fuse = S_ > 0 && lane_wpb() >= 2 && !b.no_fuse && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
   if (b.f32f) {
     // the float32 hand-off needs the fused slicer (api.cpp asks psk_lane_fused first)
     if (!(fuse && S_ != 0 && lane_wpb() == 4)) return AMR_LP_LANE;
@@ -1558,7 +1558,7 @@ bool psk_lane_fused(const PskBuffers& b, const PskParams& p) {
     return e ? (e[0] == '1' ? 1 : 0) : -1;
   }();
   const int64_t live = b.n_streams * (b.inflight > 1 ? b.inflight : 1);
-  return stat && !lp_split() && lane_wpb() == 4 && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
+  return stat && !lp_split() && lane_wpb() == 4 && !b.no_fuse && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
 }
 
 hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st,

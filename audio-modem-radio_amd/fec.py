@@ -14,11 +14,17 @@ them, with no reference counterpart:
                                         -> k_viterbi: maximum-likelihood
                                            hard-decision decoding of that code,
                                            one wavefront per codeword
+  ViterbiDecoder.decode_soft / decode_soft_batch
+                                        -> k_viterbi_soft: the same decoder on
+                                           int8 soft decisions, as
+                                           modem.qpsk_demodulate_soft gives them
 """
 from __future__ import annotations
 
 import struct
 import zlib
+
+import numpy as np
 
 import _amr
 
@@ -135,3 +141,32 @@ class ViterbiDecoder:
                                  f"(even, 2 .. {_amr.VITERBI_MAX_LEN})")
         outs, errs = _amr.viterbi_decode(datas)
         return (outs, errs) if return_errors else outs
+
+    def decode_soft(self, soft) -> bytes:
+        """decode_ml for soft decisions: one int8 per coded bit (> 0 bit 1, < 0 bit
+        0, |v| the reliability, 0 an erasure), as modem.qpsk_demodulate_soft gives
+        them.  Either the bit stream (16 n + 12 values) or the byte-aligned image
+        of the codeword (8 (2 n + 2) values, the last byte's high nibble skipped)."""
+        return self.decode_soft_batch([soft])[0]
+
+    def decode_soft_batch(self, softs, return_metrics: bool = False):
+        """decode_soft of every element in one launch: list[bytes]; with
+        return_metrics=True also list[int], the sum of |value| over the positions
+        where an input disagrees with the codeword of its decoded message."""
+        softs = [np.ascontiguousarray(s, np.int8).ravel() for s in softs]
+        for i, s in enumerate(softs):
+            if not _amr.is_soft_row_len(s.size):
+                raise ValueError(f"soft row {i}: {s.size} values is not a length of this code "
+                                 f"(16 k + 12, or 16 k >= 16; at most {_amr.VITERBI_SOFT_MAX_VALS})")
+        outs, metrics = _amr.viterbi_decode_soft(softs)
+        return (outs, metrics) if return_metrics else outs
+
+    @staticmethod
+    def soft_from_bytes(cw: bytes, mag: int = 1):
+        """The bit-stream soft form of a hard codeword of ConvolutionalEncoder.encode:
+        +mag for a 1, -mag for a 0, 16 n + 12 values (the last byte's low nibble)."""
+        a = np.frombuffer(bytes(cw), np.uint8)
+        if not _amr.is_codeword_len(a.size) or not 1 <= int(mag) <= 127:
+            raise ValueError("soft_from_bytes: a codeword of 2 n + 2 bytes and 1 <= mag <= 127")
+        bits = np.concatenate([np.unpackbits(a[:-1]), np.unpackbits(a[-1:])[4:]]).astype(np.int16)
+        return ((2 * bits - 1) * int(mag)).astype(np.int8)

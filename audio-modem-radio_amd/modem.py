@@ -120,6 +120,50 @@ def bpsk_demodulate_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_r
     return _psk_batch("bpsk", np.asarray(samples), baud, carrier, samp_rate)
 
 
+# soft-decision output (no reference counterpart): the same
+# bytes, and one int8 per bit of them -- > 0 bit 1, < 0 bit 0, |v| in 1..127
+# how far the differential product lies from the bit's decision boundary --
+# for fec.ViterbiDecoder.decode_soft_batch
+def _psk_soft_batch(kind: str, x2d: np.ndarray, baud, carrier, samp_rate):
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    x2d = _as_batch(x2d)
+    B, n = x2d.shape
+    if B == 0:
+        return [], []
+    plan = _amr.get_psk_plan(kind, n, baud, carrier, samp_rate, B)
+    outs, _, softs = (plan.demod_soft_host(x2d) if _amr.is_kernel_dtype(x2d.dtype)
+                      else plan.demod_soft_host_raw(x2d))
+    return outs, softs
+
+
+def qpsk_demodulate_soft(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """qpsk_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("qpsk_demodulate_soft expects a 1-D sample array (use qpsk_demodulate_soft_batch)")
+    outs, softs = _psk_soft_batch("qpsk", x[None, :], baud, carrier, samp_rate)
+    return outs[0], softs[0]
+
+
+def bpsk_demodulate_soft(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """bpsk_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("bpsk_demodulate_soft expects a 1-D sample array (use bpsk_demodulate_soft_batch)")
+    outs, softs = _psk_soft_batch("bpsk", x[None, :], baud, carrier, samp_rate)
+    return outs[0], softs[0]
+
+
+def qpsk_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _psk_soft_batch("qpsk", np.asarray(samples), baud, carrier, samp_rate)
+
+
+def bpsk_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    return _psk_soft_batch("bpsk", np.asarray(samples), baud, carrier, samp_rate)
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):

@@ -655,6 +655,47 @@ int amr_viterbi_decode_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t i
 int amr_viterbi_decode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, int64_t n, uint8_t *out,
                             int64_t out_stride, int64_t *out_len, int32_t *metric);
 
+/* ---- soft decisions: PSK soft output and the soft-input Viterbi decoder ----
+ * A soft value is an int8 v: v > 0 bit 1, v < 0 bit 0, |v| in 1..127 the reliability, 0 an erasure (the
+ * demodulator never emits it; the decoder takes it -- punctured codes -- and reads -128 as -127).
+ * For a differential product d = (dr, di) the sign is the bit the demodulator decides, the magnitude, in
+ * fp64 in this order with den = |dr| + |di|:  QPSK hi bit r = |dr + di| / den, lo bit r = |dr - di| / den,
+ * BPSK r = |dr| / den;  q = floor(r * 127.0 + 0.5);  1 unless q >= 1;  127 if q > 127;  else q.
+ * soft[s][j], j < 8 * out_len[s], belongs to the j-th bit of the stream's output bytes: packing soft > 0
+ * MSB-first gives out[s] again.  Only those values of a row are written.  The soft entries compute on the
+ * reference's own symbol samples: they never run the time-split layout (a plan set to it runs the row
+ * layout for the call), and they leave amr_psk_plan_last_layout() and its kin as the hard calls set them. */
+/* amr_psk_demod_host's arguments, then edges (NULL, or as amr_psk_demod_host_edges), soft [B][soft_stride],
+ * soft_stride >= 8 * amr_psk_plan_out_capacity() */
+int amr_psk_demod_soft_host(amr_psk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                            uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx,
+                            const double *edges, int8_t *soft, int64_t soft_stride);
+/* the same with device pointers, asynchronous on the plan's stream */
+int amr_psk_demod_soft_device(amr_psk_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                              uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                              const double *d_edges, int8_t *d_soft, int64_t soft_stride);
+/* the soft stage alone on given symbols (amr_psk_slice_host's counterpart): sym [n_streams][n_sym][re, im];
+ * soft [n_streams][2 (n_sym - 1)] (QPSK) or [n_streams][n_sym - 1] (BPSK), every bit from 0, no sync */
+int amr_psk_soft_host(int kind, const double *sym, int64_t n_streams, int64_t n_sym, int8_t *soft);
+/* The soft-input decoder: amr_viterbi_decode_*'s code, trellis, tie rule and traceback with the branch
+ * metric [c1 != (r1 > 0)] |r1| + [c2 != (r2 > 0)] |r2| for a step's values (r1, r2) and a branch's output
+ * bits (c1, c2); metric[i] = the sum of |r| over the positions where the decoded message's codeword
+ * disagrees with the input's sign.  With every |r| = 1 it is the hard decoder.  A row holds n_vals values
+ * after the in_offset leading ones every row skips (so it can follow a soft demodulation without a copy):
+ * n_vals % 16 == 12, the coded bit stream (two values per step), or n_vals % 16 == 0 (>= 16), the
+ * byte-aligned image of a codeword of n_vals / 8 bytes whose last byte's high nibble (four values) is
+ * skipped; at most 2^21 - 4 values. */
+/* device scratch bytes for n rows of in_stride_vals values: 512 bytes per 64 steps of the longest row */
+int64_t amr_viterbi_soft_work_bytes(int64_t in_stride_vals, int64_t n);
+/* device pointers, on the plan's stream (plan may be NULL).  A row whose length is none of the above, or
+ * exceeds in_stride - in_offset, gets out_len 0 and metric -1 and nothing else of it is touched. */
+int amr_viterbi_decode_soft_device(amr_psk_plan *plan, const int8_t *d_in, int64_t in_stride, int64_t in_offset,
+                                   const int64_t *d_in_len, int64_t n, uint8_t *d_out, int64_t out_stride,
+                                   int64_t *d_out_len, int32_t *d_metric, void *d_work, int64_t work_bytes);
+/* host pointers; a bad length is AMR_E_INVALID (the message names the row) before any device work */
+int amr_viterbi_decode_soft_host(const int8_t *in, int64_t in_stride, int64_t in_offset, const int64_t *in_len,
+                                 int64_t n, uint8_t *out, int64_t out_stride, int64_t *out_len, int32_t *metric);
+
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
  * the deviate hashed from (seed, s, i): distinct noisy batches over the same
