@@ -38,6 +38,67 @@ __device__ __forceinline__ size_t sym_index(int64_t s, int64_t n_sym, int64_t k,
   return ((size_t)((s >> 6) * 2 + comp) * (size_t)n_sym + (size_t)k) * 64 + (size_t)(s & 63);
 }
 
+// ---- policy-tagged global accesses (the lane kernels) ------
+// The lane kernels stream their intermediates: f, the checkpoints, the edge
+// rows and x come back only after far more traffic than L2 (4 MiB per XCD)
+// and the 256 MiB Infinity Cache hold, so under the default policy their
+// lines are dead on arrival and evict the few that are not (a lane's 128-B
+// line of x, the LO tables).  Each access class below can be issued
+// non-temporal instead (global_load / global_store ... nt), chosen per kernel
+// instantiation by a mask of these bits (AMR_LANE_NT); mask 0 is the default
+// policy everywhere.  The builtins take native vector types, so the 16-B pair
+// goes through v2d, not HIP's double2 struct.
+constexpr int kNtFStore = 1;    // f stores of the band-pass backward role
+constexpr int kNtFLoad = 2;     // f loads of the low-pass (forward pass and re-run)
+constexpr int kNtCk = 4;        // checkpoint and edge-row stores and loads, both filters
+constexpr int kNtX = 8;         // x tile loads of both band-pass roles
+constexpr int kNtWords = 16;    // decided-word stores of the fused low-pass
+constexpr int kNtAll = 31;
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+template <bool NT, typename V>
+__device__ __forceinline__ V ld_pol(const V* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT, typename V>
+__device__ __forceinline__ void st_pol(V* p, V v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+// a 16-B pair of doubles at p (16-B aligned)
+template <bool NT>
+__device__ __forceinline__ double2 ld_pair(const double* p) {
+  if constexpr (NT) {
+    const v2d v = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));
+    return make_double2(v.x, v.y);
+  } else {
+    return *reinterpret_cast<const double2*>(p);
+  }
+}
+template <bool NT>
+__device__ __forceinline__ void st_pair(double* p, double y0, double y1) {
+  if constexpr (NT) {
+    v2d v;
+    v.x = y0;
+    v.y = y1;
+    __builtin_nontemporal_store(v, reinterpret_cast<v2d*>(p));
+  } else {
+    *reinterpret_cast<double2*>(p) = make_double2(y0, y1);
+  }
+}
+
+// The fence between a lane kernel's forward pass and what re-reads its
+// checkpoints and edge rows.  Every reader is the writing wave itself or a
+// wave of the same workgroup behind a barrier, so workgroup scope orders all
+// there is to order; device scope (AMR_LANE_FENCE=1, the earlier form, kept
+// for A/Bs) also writes the XCD's L2 back and invalidates it, once per wave,
+// while every other wave on the XCD is streaming.
+__device__ __forceinline__ void lane_pass_fence(int dev_scope) {
+  if (dev_scope) __threadfence();
+  else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+
 typedef __attribute__((address_space(4))) const double CDouble;   // constant AS: uniform loads -> SMEM
 constexpr float kTinyHi = 0x1p-126f;            // FLT_MIN
 

@@ -44,6 +44,7 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "amr.h"
 #include "amr_internal.h"
@@ -89,7 +90,7 @@ int64_t psk_lane_lp_scratch_doubles(int64_t n_streams, int64_t n, int pad) {
 // (kernel arguments in SGPRs).  s1 = [G][nt][8][64] checkpoints, then
 // [G][edge][64] tail outputs.
 template <typename T, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_bp_lane(PskBuffers buf, PskParams p, Iir f) {
+__global__ __launch_bounds__(64 * WPB) void k_bp_lane(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
   constexpr int TB = kBpT;
   constexpr int PER = 16 / (int)sizeof(T);      // samples per 16-B load
   constexpr int NL = TB / PER;                  // 16-B loads per tile
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(64 * WPB) void k_bp_lane(PskBuffers buf, PskParams 
     ylast = df2t_step<8>(z, f, ox.right(jj));
     eb[(ne++) * 64] = ylast;
   }
-  __threadfence();                              // checkpoints / edge re-read below
+  lane_pass_fence(dev_fence);                   // checkpoints / edge: re-read below by this wave alone
 
   // ---- backward pass ------------------------------------------------------
   double zb[8];
@@ -284,8 +285,13 @@ __global__ __launch_bounds__(256) void k_bp_fwd(PskBuffers buf, PskParams p, Iir
 // F32F (PskBuffers::f32f): f is stored rounded to float32 into the first half
 // of the group's s2 slot (the f64 layout's element order, float elements),
 // and each stream's max |f| (bits: NaN / inf dominate) into buf.fpeak.
-template <typename T, int GPB, bool ZO, bool FIXUP = false, bool PRE = false, int CK = 1, bool F32F = false>
-__global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParams p, Iir f) {
+// NT: which access classes go non-temporal (psk_common.h: kNtFStore the f
+// stores, kNtCk the checkpoints and edge rows, kNtX the x tiles); 0 for the
+// PRE, CK = 2 and F32F variants.
+template <typename T, int GPB, bool ZO, bool FIXUP = false, bool PRE = false, int CK = 1, bool F32F = false, int NT = 0>
+__global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
+  static_assert(NT == 0 || (!PRE && CK == 1 && !F32F), "cache policies: the default paths only");
+  constexpr bool NTF = (NT & kNtFStore) != 0, NTC = (NT & kNtCk) != 0, NTX = (NT & kNtX) != 0;
   static_assert(!(FIXUP && PRE), "the fix-up pass runs its own forward pass");
   static_assert(!(F32F && FIXUP), "the fix-up pass writes float64 f");
   static_assert(CK == 1 || (CK == 2 && !PRE), "64-sample checkpoints: the kernel's own forward pass");
@@ -323,7 +329,8 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 
   auto load_tile = [&](int64_t t, v4u (&r)[NL]) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) r[k] = *reinterpret_cast<const v4u*>(xb + (size_t)t * TB * sizeof(T) + k * 16);
+    for (int k = 0; k < NL; ++k)
+      r[k] = ld_pol<NTX>(reinterpret_cast<const v4u*>(xb + (size_t)t * TB * sizeof(T) + k * 16));
   };
   auto tile_x = [&](const v4u (&r)[NL], int k) -> double {
     T v[PER];
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
     for (int64_t t = 0; t < nt; ++t) {
       if (t % CK == 0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) ck[((t / CK) * 8 + j) * 64] = z[j];
+        for (int j = 0; j < 8; ++j) st_pol<NTC>(&ck[((t / CK) * 8 + j) * 64], z[j]);
       }
       v4u cur[NL];
 #pragma unroll
@@ -359,10 +366,13 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
       for (int k = 0; k < TB; ++k) (void)bp_step<ZO>(z, f, tile_x(cur, k), acc);
     }
     int e = 0;
-    for (int64_t i = i_tail; i < n; ++i) eb[(e++) * 64] = bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc);
-    for (int jj = 0; jj < pad; ++jj) eb[(e++) * 64] = bp_step<ZO>(z, f, ox.right(jj), acc);
+    for (int64_t i = i_tail; i < n; ++i) st_pol<NTC>(&eb[(e++) * 64], bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc));
+    for (int jj = 0; jj < pad; ++jj) st_pol<NTC>(&eb[(e++) * 64], bp_step<ZO>(z, f, ox.right(jj), acc));
     if (bp_bad<ZO>(acc, z) && s <= last) atomicOr(&buf.bp_flags[s], 1);
-    __threadfence();                            // checkpoints + edge: read by this wave and the backward wave
+    // the checkpoints are re-read by this wave (its re-run role below), the
+    // edge rows by the backward wave of the same workgroup behind the barrier
+    // that follows: nothing stored here is read by another workgroup
+    lane_pass_fence(dev_fence);
   }
   __syncthreads();
 
@@ -429,7 +439,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
     if (active && nt > 0) {
       load_tile(nt - 1, xr);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) cn[j] = ck[((nt - 1) * 8 + j) * 64];
+      for (int j = 0; j < 8; ++j) cn[j] = ld_pol<NTC>(&ck[((nt - 1) * 8 + j) * 64]);
     }
     for (int64_t it = 0; it <= nt; ++it) {
       const int64_t t = nt - 1 - it;
@@ -443,7 +453,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
         const int64_t tp = t > 0 ? t - 1 : 0;
         load_tile(tp, xr);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) cn[j] = ck[(tp * 8 + j) * 64];
+        for (int j = 0; j < 8; ++j) cn[j] = ld_pol<NTC>(&ck[(tp * 8 + j) * 64]);
         double2 (*ybuf)[64] = yb[gi][it & 1];
         float dummy = 0.0f;                     // the re-run repeats checked steps: no detector
 #pragma unroll
@@ -467,18 +477,18 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
       }
     };
     if (active) {
-      const double ylast = eb[(ne - 1) * 64];
+      const double ylast = ld_pol<NTC>(&eb[(ne - 1) * 64]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) zb[j] = f.zi[j] * ylast;
       for (int e = ne - 1; e >= 0; --e) {
-        const double y = bp_step<ZO>(zb, f, eb[e * 64], acc);
+        const double y = bp_step<ZO>(zb, f, ld_pol<NTC>(&eb[e * 64]), acc);
         const int64_t i = i_tail + e;
         if (i < n) {
           if constexpr (F32F) {
             fo32[(i >> 1) * 64 + (i & 1)] = (float)y;
             pk_acc(y);
           } else {
-            fo[(i >> 1) * 64 + (i & 1)] = y;
+            st_pol<NTF>(&fo[(i >> 1) * 64 + (i & 1)], y);
           }
         }
       }
@@ -500,7 +510,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
             pk_acc(y0);
             pk_acc(y1);
           } else {
-            *reinterpret_cast<double2*>(fp + k * 64) = make_double2(y0, y1);
+            st_pair<NTF>(fp + k * 64, y0, y1);
           }
         }
       }
@@ -563,8 +573,14 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 // boundary -- QPSK ||di| - |dr||, BPSK |dr| against sqrt2 E (|s0|_1 + |s1|_1 +
 // E) -- into flags and bp_flags, and the fix-up band-pass, K3x and K4a redo
 // those streams exactly.
-template <int SPS, int FM, int WPB, bool FUSE = false, bool F32F = false>
-__global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lane(PskBuffers buf, PskParams p, Iir f) {
+// NT (four-wave workgroups, float64 f): which access classes go non-temporal
+// (psk_common.h: kNtFLoad the f loads, kNtCk the checkpoints and edges,
+// kNtWords the fused slicer's word stores).
+template <int SPS, int FM, int WPB, bool FUSE = false, bool F32F = false, int NT = 0>
+__global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lane(PskBuffers buf, PskParams p, Iir f,
+                                                                                 int dev_fence) {
+  static_assert(NT == 0 || (WPB == 4 && !F32F), "cache policies: the default paths only");
+  constexpr bool NTF = (NT & kNtFLoad) != 0, NTC = (NT & kNtCk) != 0, NTW = (NT & kNtWords) != 0;
   static_assert(!FUSE || (SPS > 0 && WPB >= 2), "fused slicing: static slots, both components in one workgroup");
   static_assert(!F32F || FUSE, "the float32 hand-off's margin check runs in the fused slicer");
   using FV = typename std::conditional<F32F, float2, double2>::type;
@@ -620,7 +636,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
   CDouble* const lo4 = (CDouble*)(buf.lo) + 2 * comp;                            // (mult, addend) at [4i]
   auto F = [&](int64_t i) -> double {
     if constexpr (F32F) return (double)fl32[(i >> 1) * 64 + (i & 1)];
-    else return fl[(i >> 1) * 64 + (i & 1)];
+    else return ld_pol<NTF>(&fl[(i >> 1) * 64 + (i & 1)]);
   };
   auto Xm = [&](int64_t i) { return F(i) * loc[i]; };
   // f pairs of tile t, chunk c: this lane's 16 B (F32F: 8 B) at pair t*TL/2 + c*HC + k
@@ -630,9 +646,9 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
 #pragma unroll
       for (int k = 0; k < HC; ++k) r[k] = fp[k * 32];
     } else {
-      const double2* fp = reinterpret_cast<const double2*>(fl + (size_t)(t * (TL / 2) + c * HC) * 64);
+      const double* fp = fl + (size_t)(t * (TL / 2) + c * HC) * 64;
 #pragma unroll
-      for (int k = 0; k < HC; ++k) r[k] = fp[k * 32];
+      for (int k = 0; k < HC; ++k) r[k] = ld_pair<NTF>(fp + k * 64);
     }
   };
   auto load_lo = [&](int64_t t) -> double { return lov[t * TL + (lane < TL ? lane : 0)]; };
@@ -665,14 +681,14 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
     const double e = 2.0 * x0 - Xm(pad - jj);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, e, y);
-    eh[jj * 64] = y;
+    st_pol<NTC>(&eh[jj * 64], y);
   }
   const int64_t nh = n < TL ? n : TL;           // tile 0 (holds bb[0]): edge buffer, not recomputed
   for (int64_t i = 0; i < nh; ++i) {
     const double e = i == 0 ? x0 : Xm(i);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, i == 0 ? y : e, y);
-    eh[(pad + i) * 64] = y;
+    st_pol<NTC>(&eh[(pad + i) * 64], y);
   }
   FV ring[R][HC];
   if (nt > 1) {
@@ -684,7 +700,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
     const int64_t tn = t + 1 < nt ? t + 1 : t;
     const double lon = load_lo(tn);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ck[(t * 4 + j) * 64] = z[j];
+    for (int j = 0; j < 4; ++j) st_pol<NTC>(&ck[(t * 4 + j) * 64], z[j]);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       FV fv[HC];
@@ -710,19 +726,19 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
     const double e = Xm(i);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, e, y);
-    et[(ne++) * 64] = y;
+    st_pol<NTC>(&et[(ne++) * 64], y);
   }
   double ylast = 0.0;
   for (int jj = 0; jj < pad; ++jj) {
     const double e = 2.0 * xl - Xm(n - 2 - jj);
     ylast = lp_step(z, f, e);
     acc = tiny_min3(acc, e, ylast);
-    et[(ne++) * 64] = ylast;
+    st_pol<NTC>(&et[(ne++) * 64], ylast);
   }
   bad |= !(acc >= kTinyHi);
 #pragma unroll
   for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(z[j]);
-  __threadfence();                              // checkpoints / edges re-read below
+  lane_pass_fence(dev_fence);                   // checkpoints and edges: re-read below by this wave alone
 
   // ---- backward pass ----------------------------------------------------------
   const int64_t S = p.n_sym, first = p.first, sps = p.sps;
@@ -769,13 +785,13 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
               }
               wacc |= qpsk_dibit(dr, di) << (30 - 2 * (int)(k & 15));
               if ((k & 15) == 0) {
-                if (s < buf.n_streams) buf.words[(size_t)s * p.n_words + (k >> 4)] = wacc;
+                if (s < buf.n_streams) st_pol<NTW>(&buf.words[(size_t)s * p.n_words + (k >> 4)], wacc);
                 wacc = 0;
               }
             } else {
               wacc |= (dr < 0 ? 1u : 0u) << (31 - (int)(k & 31));
               if ((k & 31) == 0) {
-                if (s < buf.n_streams) buf.words[(size_t)s * p.n_words + (k >> 5)] = wacc;
+                if (s < buf.n_streams) st_pol<NTW>(&buf.words[(size_t)s * p.n_words + (k >> 5)], wacc);
                 wacc = 0;
               }
             }
@@ -791,7 +807,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
 #pragma unroll
   for (int j = 0; j < 4; ++j) zb[j] = f.zi[j] * ylast;
   for (int e = ne - 1; e >= 0; --e) {
-    const double y = lp_step(zb, f, et[e * 64]);
+    const double y = lp_step(zb, f, ld_pol<NTC>(&et[e * 64]));
     accb = tiny_min3(accb, y, y);
     const int64_t i = i_tail + e;
     if (i < n) sym_out(i, y);
@@ -801,7 +817,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
     const int64_t q0 = SPS > 0 ? first / SPS : 0;
     double cn[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) cn[j] = ck[((nt - 1) * 4 + j) * 64];
+    for (int j = 0; j < 4; ++j) cn[j] = ld_pol<NTC>(&ck[((nt - 1) * 4 + j) * 64]);
 #pragma unroll
     for (int c = 0; c < R; ++c) load_chunk(nt - 1, c, ring[c]);
     put_lo(nt - 1, load_lo(nt - 1));
@@ -812,7 +828,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
       for (int j = 0; j < 4; ++j) zf[j] = cn[j];
       const int64_t tp = t > 1 ? t - 1 : 1;     // the next (lower) tile's input and checkpoint in flight
 #pragma unroll
-      for (int j = 0; j < 4; ++j) cn[j] = ck[(tp * 4 + j) * 64];
+      for (int j = 0; j < 4; ++j) cn[j] = ld_pol<NTC>(&ck[(tp * 4 + j) * 64]);
       const double lop = load_lo(tp);
       double yt[TL];
 #pragma unroll
@@ -848,7 +864,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
     }
   }
   for (int e = pad + (int)nh - 1; e >= 0; --e) {
-    const double y = lp_step(zb, f, eh[e * 64]);
+    const double y = lp_step(zb, f, ld_pol<NTC>(&eh[e * 64]));
     accb = tiny_min3(accb, y, y);
     const int64_t i = e - pad;
     if (i >= 0) sym_out(i, y);
@@ -891,8 +907,11 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
 //     a whole 512-B row.
 // flags are raised per stream (by either component's lane), so K3x and K4a
 // redo flagged streams as after k_lp_lane.
-template <int SPS, int FM>
-__global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf, PskParams p, Iir f) {
+// NT: which access classes go non-temporal (psk_common.h: kNtFLoad the f
+// loads, kNtCk the checkpoints and edges, kNtWords the word stores).
+template <int SPS, int FM, int NT = 0>
+__global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
+  constexpr bool NTF = (NT & kNtFLoad) != 0, NTC = (NT & kNtCk) != 0, NTW = (NT & kNtWords) != 0;
   constexpr int TL = kLpT;
   constexpr int CH = AMR_LP_CH;
   constexpr int NCH = TL / CH, HC = CH / 2;
@@ -921,12 +940,12 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
   const unsigned fo = hl * 2;
   const double* __restrict__ lov = buf.lo2 + (size_t)comp * n;                   // lo_c[i] of this lane's component
   const double* __restrict__ lo4 = buf.lo + 2 * comp;                            // (mult, addend) at [4i]
-  auto F = [&](int64_t i) -> double { return (fl + ((i >> 1) * 64 + (i & 1)))[fo]; };
+  auto F = [&](int64_t i) -> double { return ld_pol<NTF>(&(fl + ((i >> 1) * 64 + (i & 1)))[fo]); };
   auto Xm = [&](int64_t i) { return F(i) * lov[i]; };
   auto load_chunk = [&](int64_t t, int c, double2 (&r)[HC]) {
-    const double2* fp = reinterpret_cast<const double2*>(fl + (size_t)(t * (TL / 2) + c * HC) * 64);
+    const double* fp = fl + (size_t)(t * (TL / 2) + c * HC) * 64;
 #pragma unroll
-    for (int k = 0; k < HC; ++k) r[k] = fp[k * 32 + hl];
+    for (int k = 0; k < HC; ++k) r[k] = ld_pair<NTF>(&(fp + k * 64)[fo]);
   };
   // the tile's LO multipliers of both components: lanes < TL load one of each a tile ahead
   auto load_lo = [&](int64_t t) -> double2 {
@@ -965,14 +984,14 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
     const double e = 2.0 * x0 - Xm(pad - jj);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, e, y);
-    (eh + jj * 64)[lane] = y;
+    st_pol<NTC>(&(eh + jj * 64)[lane], y);
   }
   const int64_t nh = n < TL ? n : TL;           // tile 0 (holds bb[0]): edge buffer, not recomputed
   for (int64_t i = 0; i < nh; ++i) {
     const double e = i == 0 ? x0 : Xm(i);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, i == 0 ? y : e, y);
-    (eh + (pad + i) * 64)[lane] = y;
+    st_pol<NTC>(&(eh + (pad + i) * 64)[lane], y);
   }
   double2 ring[R][HC];
   if (nt > 1) {
@@ -984,7 +1003,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
     const int64_t tn = t + 1 < nt ? t + 1 : t;
     const double2 lon = load_lo(tn);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) (ck + (t * 4 + j) * 64)[lane] = z[j];
+    for (int j = 0; j < 4; ++j) st_pol<NTC>(&(ck + (t * 4 + j) * 64)[lane], z[j]);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       double2 fv[HC];
@@ -1010,19 +1029,19 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
     const double e = Xm(i);
     const double y = lp_step(z, f, e);
     acc = tiny_min3(acc, e, y);
-    (et + (ne++) * 64)[lane] = y;
+    st_pol<NTC>(&(et + (ne++) * 64)[lane], y);
   }
   double ylast = 0.0;
   for (int jj = 0; jj < pad; ++jj) {
     const double e = 2.0 * xl - Xm(n - 2 - jj);
     ylast = lp_step(z, f, e);
     acc = tiny_min3(acc, e, ylast);
-    (et + (ne++) * 64)[lane] = ylast;
+    st_pol<NTC>(&(et + (ne++) * 64)[lane], ylast);
   }
   bad |= !(acc >= kTinyHi);
 #pragma unroll
   for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(z[j]);
-  __threadfence();                              // checkpoints / edges re-read below
+  lane_pass_fence(dev_fence);                   // checkpoints and edges: re-read below by this wave alone
 
   // ---- backward pass, slicing as it goes ----------------------------------------
   const int64_t S = p.n_sym, first = p.first, sps = p.sps;
@@ -1050,13 +1069,13 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
         const double di = __builtin_fma(pr, bi, pim * br);
         wacc |= qpsk_dibit(dr, di) << (30 - 2 * (int)(k & 15));
         if ((k & 15) == 0) {
-          if (wr) (wp + (k >> 4))[wo] = wacc;
+          if (wr) st_pol<NTW>(&(wp + (k >> 4))[wo], wacc);
           wacc = 0;
         }
       } else {
         wacc |= (dr < 0 ? 1u : 0u) << (31 - (int)(k & 31));
         if ((k & 31) == 0) {
-          if (wr) (wp + (k >> 5))[wo] = wacc;
+          if (wr) st_pol<NTW>(&(wp + (k >> 5))[wo], wacc);
           wacc = 0;
         }
       }
@@ -1072,7 +1091,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
 #pragma unroll
   for (int j = 0; j < 4; ++j) zb[j] = f.zi[j] * ylast;
   for (int e = ne - 1; e >= 0; --e) {
-    const double y = lp_step(zb, f, (et + e * 64)[lane]);
+    const double y = lp_step(zb, f, ld_pol<NTC>(&(et + e * 64)[lane]));
     accb = tiny_min3(accb, y, y);
     const int64_t i = i_tail + e;
     if (i < n) sym_out(i, y);
@@ -1081,7 +1100,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
     const int64_t q0 = first / SPS;
     double cn[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) cn[j] = (ck + ((nt - 1) * 4 + j) * 64)[lane];
+    for (int j = 0; j < 4; ++j) cn[j] = ld_pol<NTC>(&(ck + ((nt - 1) * 4 + j) * 64)[lane]);
 #pragma unroll
     for (int c = 0; c < R; ++c) load_chunk(nt - 1, c, ring[c]);
     put_lo(nt - 1, load_lo(nt - 1));
@@ -1116,7 +1135,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
         if (k == TL - 7) lop = load_lo(tp);
         if (k == TL - 11) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) cn[j] = (ck + (tp * 4 + j) * 64)[lane];
+          for (int j = 0; j < 4; ++j) cn[j] = ld_pol<NTC>(&(ck + (tp * 4 + j) * 64)[lane]);
         }
         if (k % SPS == FM) slice(kt + (k - FM) / SPS, y1);
         if ((k - 1) % SPS == FM) slice(kt + (k - 1 - FM) / SPS, y0);
@@ -1125,7 +1144,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
     }
   }
   for (int e = pad + (int)nh - 1; e >= 0; --e) {
-    const double y = lp_step(zb, f, (eh + e * 64)[lane]);
+    const double y = lp_step(zb, f, ld_pol<NTC>(&(eh + e * 64)[lane]));
     accb = tiny_min3(accb, y, y);
     const int64_t i = e - pad;
     if (i >= 0) sym_out(i, y);
@@ -1377,6 +1396,41 @@ static int lane_wpb() {
   return v;
 }
 
+// Cache policy of the streamed intermediates (psk_common.h): AMR_LANE_NT=<mask
+// of the kNt* classes>, 0 = the default policy everywhere; unset = the
+// measured choice (profiles/lane_nt_ab.txt): f stores, f
+// loads, checkpoints and edge rows.  Non-temporal x loads cost 36 % of the
+// step (a lane's 128-B line is consumed by 8 loads) and non-temporal word
+// stores write 11 % more bytes for no time, so both keep the default policy.
+// Only the masks compiled in can be asked for (each one is another
+// instantiation of every default-path kernel): the default, 0, and every class
+// at once for the parity tests; any other value fails the launch.
+#ifndef AMR_LANE_NT_DEFAULT
+#define AMR_LANE_NT_DEFAULT (kNtFStore | kNtFLoad | kNtCk)
+#endif
+#ifndef AMR_LANE_NT_MASKS
+#define AMR_LANE_NT_MASKS 0, AMR_LANE_NT_DEFAULT, kNtAll
+#endif
+static int lane_nt() {
+  static const int v = [] { const char* e = getenv("AMR_LANE_NT"); return e ? atoi(e) : AMR_LANE_NT_DEFAULT; }();
+  return v;
+}
+template <typename Fn, int... M>
+static bool lane_nt_switch(int m, Fn&& fn, std::integer_sequence<int, M...>) {
+  return ((m == M ? (fn(std::integral_constant<int, M>{}), true) : false) || ...);
+}
+// fn(std::integral_constant<int, mask>) for the mask in force; false: that mask is not compiled in
+template <typename Fn>
+static bool with_lane_nt(Fn&& fn) {
+  return lane_nt_switch(lane_nt(), fn, std::integer_sequence<int, AMR_LANE_NT_MASKS>{});
+}
+
+static int lane_dev_fence() {
+  // AMR_LANE_FENCE=1: the device-scope fence after a forward pass (lane_pass_fence, psk_common.h)
+  static const int v = [] { const char* e = getenv("AMR_LANE_FENCE"); return e && e[0] == '1' ? 1 : 0; }();
+  return v;
+}
+
 static int bp_split() {
   // role-split band-pass (k_bp_lane2): AMR_BP_SPLIT=0 turns it off
   static const int v = [] { const char* e = getenv("AMR_BP_SPLIT"); return e && e[0] == '0' ? 0 : 1; }();
@@ -1415,8 +1469,8 @@ static hipError_t launch_bp(const PskBuffers& b, const PskParams& p, const Iir& 
     hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((g + 1) / 2)), block(256);
-    if (bp_zero_taps(p)) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 1, true>), grid, block, 0, st, b, p, f);
-    else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 1, true>), grid, block, 0, st, b, p, f);
+    if (bp_zero_taps(p)) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
+    else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
     return hipGetLastError();
   }
   if (bp_split()) {
@@ -1430,29 +1484,41 @@ static hipError_t launch_bp(const PskBuffers& b, const PskParams& p, const Iir& 
       const dim3 fgrid((unsigned)((g + 3) / 4));
       if (zo) {
         hipLaunchKernelGGL((k_bp_fwd<T, true>), fgrid, dim3(256), 0, st, b, p, f);
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, true>), grid, block, 0, st, b, p, f);
+        hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
       } else {
         hipLaunchKernelGGL((k_bp_fwd<T, false>), fgrid, dim3(256), 0, st, b, p, f);
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, true>), grid, block, 0, st, b, p, f);
+        hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
       }
     } else if (lane_wpb() >= 2 && bp_ck() == 2) {
-      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 2>), grid, block, 0, st, b, p, f);
-      else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 2>), grid, block, 0, st, b, p, f);
+      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 2>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 2>), grid, block, 0, st, b, p, f, lane_dev_fence());
     } else if (lane_wpb() >= 2) {
-      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 2, true>), grid, block, 0, st, b, p, f);
-      else hipLaunchKernelGGL((k_bp_lane2<T, 2, false>), grid, block, 0, st, b, p, f);
+      // the default path: the cache policies of AMR_LANE_NT (its fix-up launch below inherits them)
+      const bool ok = with_lane_nt([&](auto m) {
+        constexpr int NT = decltype(m)::value;
+        if (zo)
+          hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 1, false, NT>), grid, block, 0, st, b, p, f,
+                             lane_dev_fence());
+        else
+          hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 1, false, NT>), grid, block, 0, st, b, p, f,
+                             lane_dev_fence());
+        if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
+          hipLaunchKernelGGL((k_bp_lane2<T, 1, false, true, false, 1, false, NT>), dim3((unsigned)g), dim3(128), 0, st, b,
+                             p, f, lane_dev_fence());
+      });
+      return ok ? hipGetLastError() : hipErrorInvalidValue;
     } else {
-      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 1, true>), grid, block, 0, st, b, p, f);
-      else hipLaunchKernelGGL((k_bp_lane2<T, 1, false>), grid, block, 0, st, b, p, f);
+      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      else hipLaunchKernelGGL((k_bp_lane2<T, 1, false>), grid, block, 0, st, b, p, f, lane_dev_fence());
     }
     if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
-      hipLaunchKernelGGL((k_bp_lane2<T, 1, false, true>), dim3((unsigned)g), dim3(128), 0, st, b, p, f);
+      hipLaunchKernelGGL((k_bp_lane2<T, 1, false, true>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
     return hipGetLastError();
   }
   switch (lane_wpb()) {
-    case 4: hipLaunchKernelGGL((k_bp_lane<T, 4>), dim3((unsigned)((g + 3) / 4)), dim3(256), 0, st, b, p, f); break;
-    case 2: hipLaunchKernelGGL((k_bp_lane<T, 2>), dim3((unsigned)((g + 1) / 2)), dim3(128), 0, st, b, p, f); break;
-    default: hipLaunchKernelGGL((k_bp_lane<T, 1>), dim3((unsigned)g), dim3(64), 0, st, b, p, f);
+    case 4: hipLaunchKernelGGL((k_bp_lane<T, 4>), dim3((unsigned)((g + 3) / 4)), dim3(256), 0, st, b, p, f, lane_dev_fence()); break;
+    case 2: hipLaunchKernelGGL((k_bp_lane<T, 2>), dim3((unsigned)((g + 1) / 2)), dim3(128), 0, st, b, p, f, lane_dev_fence()); break;
+    default: hipLaunchKernelGGL((k_bp_lane<T, 1>), dim3((unsigned)g), dim3(64), 0, st, b, p, f, lane_dev_fence());
   }
   return hipGetLastError();
 }
@@ -1473,9 +1539,9 @@ hipError_t launch_psk_bandpass_fixup(const PskBuffers& b, const PskParams& p, co
   if (f.nt != 9) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((b.n_streams + 63) / 64)), block(128);
   switch (b.dtype) {
-    case kF32: hipLaunchKernelGGL((k_bp_lane2<float, 1, false, true>), grid, block, 0, st, b, p, f); break;
-    case kF64: hipLaunchKernelGGL((k_bp_lane2<double, 1, false, true>), grid, block, 0, st, b, p, f); break;
-    case kI16: hipLaunchKernelGGL((k_bp_lane2<int16_t, 1, false, true>), grid, block, 0, st, b, p, f); break;
+    case kF32: hipLaunchKernelGGL((k_bp_lane2<float, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
+    case kF64: hipLaunchKernelGGL((k_bp_lane2<double, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
+    case kI16: hipLaunchKernelGGL((k_bp_lane2<int16_t, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1521,28 +1587,41 @@ static int launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hipS
   if (b.f32f) {
     // the float32 hand-off needs the fused slicer (api.cpp asks psk_lane_fused first)
     if (!(fuse && S_ != 0 && lane_wpb() == 4)) return AMR_LP_LANE;
-    hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, S_ != 0>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
+    hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, S_ != 0>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f, lane_dev_fence());
     return AMR_LP_LANE_FUSED;
   }
   if constexpr (S_ != 0) {
     // (k_lp_lane_h offsets a half's words by a 32-bit lane term: 32 * n_words must fit)
     if (fuse && lane_wpb() == 4 && lp_half() && p.n_words < (1 << 26)) {
-      hipLaunchKernelGGL((k_lp_lane_h<S_, F_>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
-      return AMR_LP_LANE_HALF;
+      const bool ok = with_lane_nt([&](auto m) {
+        hipLaunchKernelGGL((k_lp_lane_h<S_, F_, decltype(m)::value>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b,
+                           p, f, lane_dev_fence());
+      });
+      return ok ? AMR_LP_LANE_HALF : -1;
     }
   }
   switch (lane_wpb()) {
-    case 4:
-      if (fuse) hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
-      else hipLaunchKernelGGL((k_lp_lane<S_, F_, 4>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f);
+    case 4: {
+      // (under 32768 live streams, the soft-output calls, AMR_LP_HALF=0: the same cache policies)
+      const bool ok = with_lane_nt([&](auto m) {
+        constexpr int NT = decltype(m)::value;
+        if (fuse)
+          hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, false, NT>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st,
+                             b, p, f, lane_dev_fence());
+        else
+          hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, false, false, NT>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b,
+                             p, f, lane_dev_fence());
+      });
+      if (!ok) return -1;
       break;
+    }
     case 2:
-      if (fuse) hipLaunchKernelGGL((k_lp_lane<S_, F_, 2, S_ != 0>), dim3((unsigned)g), dim3(128), 0, st, b, p, f);
-      else hipLaunchKernelGGL((k_lp_lane<S_, F_, 2>), dim3((unsigned)g), dim3(128), 0, st, b, p, f);
+      if (fuse) hipLaunchKernelGGL((k_lp_lane<S_, F_, 2, S_ != 0>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
+      else hipLaunchKernelGGL((k_lp_lane<S_, F_, 2>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
       break;
     default:
       // a multiple of 16 blocks: the re/im XCD pairing is a bijection
-      hipLaunchKernelGGL((k_lp_lane<S_, F_, 1>), dim3((unsigned)((2 * g + 15) / 16 * 16)), dim3(64), 0, st, b, p, f);
+      hipLaunchKernelGGL((k_lp_lane<S_, F_, 1>), dim3((unsigned)((2 * g + 15) / 16 * 16)), dim3(64), 0, st, b, p, f, lane_dev_fence());
   }
   return fuse ? AMR_LP_LANE_FUSED : AMR_LP_LANE;
 }
@@ -1579,6 +1658,7 @@ hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, cons
   else if (p.sps == 5 && fm == 0) fused = launch_lp<5, 0>(b, p, f, st);
   else if (p.sps == 20 && fm == 0) fused = launch_lp<20, 0>(b, p, f, st);
   else fused = launch_lp<0, 0>(b, p, f, st);
+  if (fused < 0) return hipErrorInvalidValue;   // an AMR_LANE_NT mask that is not compiled in
   if (sliced) *sliced = fused != AMR_LP_LANE;
   if (kernel) *kernel = fused;
   return hipGetLastError();
