@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "api_common.h"
 #include "dev_mem.h"
 #include "iir_design.h"
+#include "plan_core.h"
 #include "split_strict.h"
 
 namespace amr {
@@ -212,10 +214,11 @@ constexpr int64_t kSplitConvMinL = 128;
 constexpr int64_t kSplitConvMaxL = 1024;
 constexpr int64_t kSplitConvChunks = 3072;
 
-struct amr_psk_plan {
-  std::mutex mu;
-  int device = 0;
-  hipStream_t stream = nullptr;
+// the stages AMR_SYNC_EACH_KERNEL=1 synchronises after (AMR_T_BANDPASS .. AMR_T_FEC)
+static const char* const kPskSlotNames[] = {"bandpass", "lowpass_fwd", "lowpass_bwd", "lowpass_exact", "slice+sync_pack", "fec"};
+
+struct amr_psk_plan : PlanCore<AMR_T_COUNT> {
+  amr_psk_plan() { sync_names = kPskSlotNames; n_sync_names = 6; }
   PskParams p{};
   Iir bp{}, lp{};
   bool lp_exact_only = false;   // low-pass coefficients outside the separable proof
@@ -242,14 +245,9 @@ struct amr_psk_plan {
   } mem;
   double* s1 = nullptr;   // = s1_base + kFrontSlack (backward prefetch may read below)
   double* s3 = nullptr;   // = s3_base + kFrontSlack
-  // timing
-  bool timing = false;
   int inflight = 1;             // amr_psk_plan_set_inflight hint
   int last_layout = 0;          // AMR_LAYOUT_* of the last call
-  hipEvent_t ev[AMR_T_COUNT + 1][2]{};
-  bool ev_used[AMR_T_COUNT]{};
   int64_t last_exact = 0;
-  GatherGate gate;              // an all-gather still reading this plan's outputs
   // time-split layout (psk_split_kernels.hip): designed on first use
   int forced_layout = -1;       // amr_psk_plan_set_layout (-1: by streams in flight)
   bool split_designed = false, split_ok = false;
@@ -385,10 +383,7 @@ int64_t psk_max_bytes(const amr_psk_plan* pl, int64_t allocated) {
 // small instead of handing the kernels freed memory.
 int grow_scratch(amr_psk_plan* pl, DevBuf& buf, int64_t want) {
   if (buf.bytes() >= want && buf) return AMR_OK;
-  static const bool fail_grow = [] {             // test hook: make every grow fail
-    const char* e = std::getenv("AMR_TEST_FAIL_SCRATCH_GROW");
-    return e && e[0] == '1';
-  }();
+  static const bool fail_grow = env_on("AMR_TEST_FAIL_SCRATCH_GROW");   // test hook: make every grow fail
   HIP_TRY(hipStreamSynchronize(pl->stream));     // queued work may still use the old block
   DevBuf nb;
   hipError_t e = fail_grow ? hipErrorOutOfMemory : nb.reserve(want, nullptr);
@@ -437,15 +432,11 @@ namespace {
 void split_design(amr_psk_plan* pl);   // below, with run_psk
 bool split_conv_on(const amr_psk_plan* pl);
 bool split_strict_on(const amr_psk_plan* pl);
-int strict_prepare(amr_psk_plan* pl);
 bool split_design_core(const Iir& bp, const Iir& lp, int64_t n, int64_t n_sym, int64_t* w1, int64_t* w2,
                        double* kappa);
 double f32_design(const Iir& lp);
 int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, int64_t L,
                         double* ebound = nullptr);
-int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
-                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx, int8_t* soft = nullptr,
-                   int64_t soft_stride = 0);
 }  // namespace
 
 extern "C" {
@@ -506,9 +497,7 @@ static void plan_free(amr_psk_plan* pl) {
   if (pl->stream) (void)hipStreamSynchronize(pl->stream);
   gate_free(pl->gate);
   pl->mem = amr_psk_plan::Mem{};                 // frees every device buffer
-  for (auto& e : pl->ev)
-    for (auto& h : e)
-      if (h) (void)hipEventDestroy(h);
+  core_destroy_events(*pl);
   if (pl->stream) (void)hipStreamDestroy(pl->stream);
   delete pl;
 }
@@ -544,12 +533,8 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
   // kernels then form each distinct product x * b[i] once (psk_lane_kernels.hip)
   p.bp_sym = bp_nt == 9 && same_bits(bp_b[8], bp_b[0]) && same_bits(bp_b[6], bp_b[2]) ? 1 : 0;
   p.lp_sym = lp_nt == 5 && same_bits(lp_b[4], lp_b[0]) && same_bits(lp_b[3], lp_b[1]) ? 1 : 0;
-  pl->bp.nt = bp_nt;
-  pl->lp.nt = lp_nt;
-  for (int i = 0; i < bp_nt; ++i) { pl->bp.b[i] = bp_b[i]; pl->bp.a[i] = bp_a[i]; }
-  for (int i = 0; i < bp_nt - 1; ++i) pl->bp.zi[i] = bp_zi[i];
-  for (int i = 0; i < lp_nt; ++i) { pl->lp.b[i] = lp_b[i]; pl->lp.a[i] = lp_a[i]; }
-  for (int i = 0; i < lp_nt - 1; ++i) pl->lp.zi[i] = lp_zi[i];
+  pl->bp = make_iir(bp_b, bp_a, bp_zi, bp_nt);
+  pl->lp = make_iir(lp_b, lp_a, lp_zi, lp_nt);
   // separable low-pass proof needs b > 0 normal and zi, a normal non-zero
   for (int i = 0; i < lp_nt; ++i) {
     if (!(lp_b[i] > 0.0 && std::isnormal(lp_b[i]) && lp_b[i] >= 0x1p-50)) pl->lp_exact_only = true;
@@ -557,9 +542,8 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
   }
   for (int i = 0; i < lp_nt - 1; ++i)
     if (!std::isnormal(lp_zi[i])) pl->lp_exact_only = true;
-  // test hook: route every stream through the exact complex low-pass kernel
-  if (const char* f = std::getenv("AMR_FORCE_EXACT_LOWPASS"))
-    if (f[0] == '1') pl->lp_exact_only = true;
+  // test hook, read at every creation: route every stream through the exact complex low-pass kernel
+  if (env_on("AMR_FORCE_EXACT_LOWPASS")) pl->lp_exact_only = true;
   p.f32_margin = bp_nt == 9 && p.lp_sym ? f32_design(pl->lp) : 0.0;
 
   amr_psk_plan::Mem& m = pl->mem;
@@ -627,23 +611,12 @@ int64_t amr_psk_plan_bytes_estimate(int kind, int64_t n, int64_t sps, int64_t fi
 
 int amr_psk_plan_synchronize(amr_psk_plan* plan) {
   if (!plan) return fail(AMR_E_INVALID, "plan is NULL");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  HIP_TRY(gate_sync(plan->gate));
-  return AMR_OK;
+  return core_synchronize(*plan);
 }
 
 int amr_psk_plan_enable_timing(amr_psk_plan* plan, int on) {
   if (!plan) return fail(AMR_E_INVALID, "plan is NULL");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (on && !plan->ev[0][0]) {
-    for (auto& e : plan->ev)
-      for (auto& h : e) HIP_TRY(hipEventCreate(&h));
-  }
-  plan->timing = on != 0;
-  return AMR_OK;
+  return core_enable_timing(*plan, on);
 }
 
 int amr_psk_plan_set_inflight(amr_psk_plan* plan, int batches) {
@@ -656,16 +629,7 @@ int amr_psk_plan_set_inflight(amr_psk_plan* plan, int batches) {
 
 int amr_psk_plan_timings(amr_psk_plan* plan, float* ms, int count) {
   if (!plan || !ms) return fail(AMR_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  for (int i = 0; i < count && i < AMR_T_COUNT; ++i) {
-    ms[i] = -1.0f;
-    if (!plan->timing || !plan->ev_used[i]) continue;
-    HIP_TRY(hipEventSynchronize(plan->ev[i][1]));   // the launch slot may end on a comm stream (a gather)
-    HIP_TRY(hipEventElapsedTime(&ms[i], plan->ev[i][0], plan->ev[i][1]));
-  }
-  return AMR_OK;
+  return core_timings(*plan, ms, count);
 }
 
 int amr_psk_plan_last_layout(const amr_psk_plan* plan) { return plan ? plan->last_layout : -1; }
@@ -684,11 +648,7 @@ int amr_psk_split_design(const double* bp_b, const double* bp_a, int bp_nt, cons
   if (!bp_b || !bp_a || !lp_b || !lp_a || !warmup_bp || !warmup_lp || !kappa || bp_nt < 2 || bp_nt > kMaxTaps ||
       lp_nt < 2 || lp_nt > kMaxTaps || n < 1 || n_sym < 0)
     return fail(AMR_E_INVALID, "amr_psk_split_design: bad argument");
-  Iir bp{}, lp{};
-  bp.nt = bp_nt;
-  lp.nt = lp_nt;
-  for (int i = 0; i < bp_nt; ++i) { bp.b[i] = bp_b[i]; bp.a[i] = bp_a[i]; }
-  for (int i = 0; i < lp_nt; ++i) { lp.b[i] = lp_b[i]; lp.a[i] = lp_a[i]; }
+  const Iir bp = make_iir(bp_b, bp_a, nullptr, bp_nt), lp = make_iir(lp_b, lp_a, nullptr, lp_nt);
   *warmup_bp = *warmup_lp = -1;
   *kappa = -1.0;
   if (!split_design_core(bp, lp, n, n_sym, warmup_bp, warmup_lp, kappa)) {
@@ -701,10 +661,7 @@ int amr_psk_split_design(const double* bp_b, const double* bp_a, int bp_nt, cons
 
 double amr_psk_f32_margin(const double* lp_b, const double* lp_a, int lp_nt) {
   if (!lp_b || !lp_a || lp_nt != 5) return 0.0;
-  Iir lp{};
-  lp.nt = lp_nt;
-  for (int i = 0; i < lp_nt; ++i) { lp.b[i] = lp_b[i]; lp.a[i] = lp_a[i]; }
-  return f32_design(lp);
+  return f32_design(make_iir(lp_b, lp_a, nullptr, lp_nt));
 }
 
 int amr_psk_split_symbols_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
@@ -786,13 +743,7 @@ int amr_psk_split_strict_design(const double* bp_b, const double* bp_a, const do
   if (!bp_b || !bp_a || !bp_zi || !lp_b || !lp_a || !lp_zi || !consts || bp_nt != 9 || lp_nt != 5 || n < 1 ||
       sps < 1 || first < 0)
     return fail(AMR_E_INVALID, "amr_psk_split_strict_design: bad argument");
-  Iir bp{}, lp{};
-  bp.nt = bp_nt;
-  lp.nt = lp_nt;
-  for (int i = 0; i < bp_nt; ++i) { bp.b[i] = bp_b[i]; bp.a[i] = bp_a[i]; }
-  for (int i = 0; i < bp_nt - 1; ++i) bp.zi[i] = bp_zi[i];
-  for (int i = 0; i < lp_nt; ++i) { lp.b[i] = lp_b[i]; lp.a[i] = lp_a[i]; }
-  for (int i = 0; i < lp_nt - 1; ++i) lp.zi[i] = lp_zi[i];
+  const Iir bp = make_iir(bp_b, bp_a, bp_zi, bp_nt), lp = make_iir(lp_b, lp_a, lp_zi, lp_nt);
   const int64_t n_sym = n > first ? (n - first + sps - 1) / sps : 0;
   int64_t w1 = 0, w2 = 0;
   double kappa = 0.0;
@@ -825,11 +776,7 @@ int amr_split_state_tables(const double* b, const double* a, const double* zi, i
                            double* Z0) {
   if (!b || !a || !zi || !K || !Z0 || nt < 2 || nt > kMaxTaps || w < 0)
     return fail(AMR_E_INVALID, "amr_split_state_tables: bad argument");
-  Iir f{};
-  f.nt = nt;
-  for (int i = 0; i < nt; ++i) { f.b[i] = b[i]; f.a[i] = a[i]; }
-  for (int i = 0; i < nt - 1; ++i) f.zi[i] = zi[i];
-  split_state_tables(f, w, K, Z0);
+  split_state_tables(make_iir(b, a, zi, nt), w, K, Z0);
   return AMR_OK;
 }
 
@@ -923,23 +870,19 @@ bool split_design_core(const Iir& bp, const Iir& lp, int64_t n, int64_t n_sym, i
 // outputs, and long enough to keep a batch within kSplitLanes lanes)
 // AMR_PSK_SPLIT_CONV=0: the w1-step warm-ups instead of KS0's convolution
 bool split_conv_on(const amr_psk_plan* pl) {
-  static const bool conv_env = [] { const char* e = std::getenv("AMR_PSK_SPLIT_CONV"); return !(e && e[0] == '0'); }();
+  static const bool conv_env = env_not_off("AMR_PSK_SPLIT_CONV");
   return conv_env && pl->mem.split_tab.as<double>() && pl->bp.nt == 9;
 }
 // the strict bound for this plan's split calls: amr_psk_plan_set_split_strict,
 // else AMR_PSK_SPLIT_STRICT=1 (off by default: DESIGN.md §3.3)
 bool split_strict_on(const amr_psk_plan* pl) {
-  static const bool env = [] { const char* e = std::getenv("AMR_PSK_SPLIT_STRICT"); return e && e[0] == '1'; }();
+  static const bool env = env_on("AMR_PSK_SPLIT_STRICT");
   return pl->strict_mode >= 0 ? pl->strict_mode == 1 : env;
 }
 PskSplit split_params(amr_psk_plan* pl, int64_t B, int64_t L) {
   PskSplit sp{};
   // AMR_PSK_SPLIT_MINL: a fixed minimum chunk length instead of the rules (an A/B knob)
-  static const int64_t min_l = [] {
-    const char* e = std::getenv("AMR_PSK_SPLIT_MINL");
-    const long v = e ? std::atol(e) : 0;
-    return v >= 8 && v <= 65536 ? (int64_t)v : 0;
-  }();
+  static const int64_t min_l = env_int("AMR_PSK_SPLIT_MINL", 8, 65536, 0);
   sp.conv = split_conv_on(pl) ? 1 : 0;
   const int64_t lanes = (B * pl->p.m1 + kSplitLanes - 1) / kSplitLanes;
   if (L > 0) sp.L = L;
@@ -1051,229 +994,236 @@ int ensure_split_zs(amr_psk_plan* pl, const PskSplit& sp, int64_t B) {
   return AMR_OK;
 }
 
-// Launch the whole PSK pipeline on plan->stream.  Caller holds plan->mu.
-// d_edge: the band-pass's odd-extension table [B][2 pad1] of a raw-integer
-// capture (odd_ext.h), or null
-// d_soft: non-null, the soft values too [B][soft_stride] (K4s).
-// They are defined on the reference's own symbol samples, so such a call runs
-// a layout that leaves those in s1: the row layout in place of the time-split
-// one (whose unflagged streams hold approximations), the lane layout with
-// K4a instead of its fused slicer.
-int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, uint8_t* d_out,
-            int64_t out_stride, int64_t* d_len, int64_t* d_sync, uint8_t* d_fec, int64_t fec_stride,
-            int64_t* d_fec_len, int32_t* d_crc, const double* d_edge = nullptr, int8_t* d_soft = nullptr,
-            int64_t soft_stride = 0) {
-  if (B < 0 || B > pl->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  if (dtype_size(dtype) == 0) return fail(AMR_E_INVALID, "unknown dtype");
-  if (x_stride < pl->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < pl->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  for (bool& u : pl->ev_used) u = false;
-  pl->last_exact = B;
-  if (B == 0) return AMR_OK;
-  hipStream_t st = pl->stream;
-  if (pl->timing) {
-    pl->ev_used[AMR_T_LAUNCH] = true;
-    HIP_TRY(hipEventRecord(pl->ev[AMR_T_LAUNCH][0], st));
+// The split layout's prologue: this call's geometry in *sp, the start-state
+// and strict scratch grown for B streams, the peaks / flags / count (and the
+// strict maxima) zeroed on the stream.  want_bounds (the diagnostic,
+// amr_psk_split_bounds_host): the strict bound whatever the plan's mode --
+// strict_mode is 1 while the geometry is made and restored on every path.
+int split_begin(amr_psk_plan* pl, int64_t B, int64_t L, bool want_bounds, PskSplit* out) {
+  const int saved = pl->strict_mode;
+  if (want_bounds) {
+    pl->strict_mode = 1;
+    if (int rc = strict_prepare(pl)) { pl->strict_mode = saved; return rc; }
   }
-  // Layout: one stream per lane (psk_lane_kernels.hip) once
-  // enough streams are in flight on the device to give it waves -- it does
-  // a third of the arithmetic per stream -- else the state-per-lane kernels
-  // (more waves per stream, lower latency).  AMR_PSK_LANE=0/1 forces either.
-  // The time-split layout (psk_split_kernels.hip, §3.3) for one capture or a
-  // few: chunk-parallel passes, margin-checked decisions, the serial row
-  // kernels behind them for a flagged batch.  AMR_PSK_SPLIT=0/1 (and
-  // amr_psk_plan_set_layout, which overrides every switch) force it off / on.
-  static const int lane_force = [] {
-    const char* e = std::getenv("AMR_PSK_LANE");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  static const int split_force = [] {
-    const char* e = std::getenv("AMR_PSK_SPLIT");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
+  PskSplit sp = split_params(pl, B, L);
+  pl->strict_mode = saved;
+  if (want_bounds && !sp.strict)
+    return fail(AMR_E_INVALID, "no strict bound for this plan (no convolution starts or design)");
+  if (int rc = ensure_split_zs(pl, sp, B)) return rc;
+  if (int rc = ensure_strict_sc(pl, sp, B)) return rc;
+  sp.zs = pl->mem.split_zs.as<double>();
+  // peaks, flags, count
+  HIP_TRY(hipMemsetAsync(pl->mem.split_peak.get(), 0, (size_t)pl->max_streams * 12 + 4, pl->stream));
+  if (sp.strict) HIP_TRY(hipMemsetAsync(sp.bnd, 0, (size_t)B * 64, pl->stream));
+  *out = sp;
+  return AMR_OK;
+}
+
+// One demod call on device buffers: the batch (io) and the optional extras
+struct PskCall {
+  DemodIo io;
+  // out non-null: FEC-decode the bytes too [B][stride]
+  struct { uint8_t* out = nullptr; int64_t stride = 0; int64_t* len = nullptr; int32_t* crc = nullptr; } fec;
+  // the band-pass's odd-extension table [B][2 pad1] of a raw-integer capture (odd_ext.h), or null
+  const double* edge = nullptr;
+  // ptr non-null: the soft values too [B][stride] (K4s).  They
+  // are defined on the reference's own symbol samples, so such a call runs a
+  // layout that leaves those in s1: the row layout in place of the time-split
+  // one (whose unflagged streams hold approximations), the lane layout with
+  // K4a instead of its fused slicer.
+  struct { int8_t* ptr = nullptr; int64_t stride = 0; } soft;
+};
+
+// Layout: one stream per lane (psk_lane_kernels.hip) once
+// enough streams are in flight on the device to give it waves -- it does
+// a third of the arithmetic per stream -- else the state-per-lane kernels
+// (more waves per stream, lower latency).  AMR_PSK_LANE=0/1 forces either.
+// The time-split layout (psk_split_kernels.hip, §3.3) for one capture or a
+// few: chunk-parallel passes, margin-checked decisions, the serial row
+// kernels behind them for a flagged batch.  AMR_PSK_SPLIT=0/1 (and
+// amr_psk_plan_set_layout, which overrides every switch) force it off / on.
+// The split design is made here, on the first call that would split.
+int pick_layout(amr_psk_plan* pl, int64_t B, bool soft) {
+  static const int lane_force = env_tri("AMR_PSK_LANE");
+  static const int split_force = env_tri("AMR_PSK_SPLIT");
   const int64_t live = B * (pl->inflight > 1 ? pl->inflight : 1);
-  // the lane kernels are written for butter(4) band-pass / low-pass
-  // coefficient shapes: 9 taps and a palindromic 5-tap low-pass
-  const bool lane_ok = pl->bp.nt == 9 && pl->p.lp_sym;
   int layout;
   if (pl->forced_layout >= 0) layout = pl->forced_layout;
   else if (lane_force >= 0) layout = lane_force == 1 ? AMR_LAYOUT_LANE : AMR_LAYOUT_ROW;
   else if (split_force == 1) layout = AMR_LAYOUT_SPLIT;
   else if (live >= kLaneMinLiveStreams) layout = AMR_LAYOUT_LANE;
   else layout = split_force != 0 && live <= kSplitMaxLiveStreams ? AMR_LAYOUT_SPLIT : AMR_LAYOUT_ROW;
-  if (layout == AMR_LAYOUT_LANE && !lane_ok) layout = AMR_LAYOUT_ROW;
-  if (layout == AMR_LAYOUT_SPLIT && d_soft) layout = AMR_LAYOUT_ROW;
+  // the lane kernels are written for butter(4) band-pass / low-pass
+  // coefficient shapes: 9 taps and a palindromic 5-tap low-pass
+  if (layout == AMR_LAYOUT_LANE && !(pl->bp.nt == 9 && pl->p.lp_sym)) layout = AMR_LAYOUT_ROW;
+  if (layout == AMR_LAYOUT_SPLIT && soft) layout = AMR_LAYOUT_ROW;
   if (layout == AMR_LAYOUT_SPLIT) {
     if (!pl->split_designed) split_design(pl);
     if (!pl->split_ok || B > 65535 || pl->p.n_sym < 2) layout = AMR_LAYOUT_ROW;
   }
-  const bool lane = layout == AMR_LAYOUT_LANE;
-  pl->last_layout = layout;
-  pl->last_lowpass = -1;
-  if (pl->p.n_sym >= 2) {
-    // the sizes this layout's kernels assume (the row layout's full-length
-    // intermediates are allocated on its first call; the time-split layout
-    // keeps its passes' outputs in the same buffers and runs the row kernels
-    // behind them); a plan whose earlier grow failed re-tries here and fails
-    // cleanly if it still cannot
-    const int64_t b1 = kFrontSlack * 8 + (lane ? lane_s1_bytes(pl) : row_s1_bytes(pl));
-    const int64_t b3 = kFrontSlack * 8 + (lane ? lane_s3_bytes(pl) : row_s3_bytes(pl));
-    if (int rc = ensure_scratch(pl, b1, b3)) return rc;
-  }
+  return layout;
+}
+
+// the kernels' view of the call and the plan's scratch (after ensure_scratch: s1 / s3 may move)
+PskBuffers psk_buffers(amr_psk_plan* pl, const PskCall& c) {
   PskBuffers b{};
-  b.x = d_x;
-  b.x_stride = x_stride;
-  b.dtype = dtype;
-  b.n_streams = B;
+  b.x = c.io.x;
+  b.x_stride = c.io.x_stride;
+  b.dtype = c.io.dtype;
+  b.n_streams = c.io.B;
   b.inflight = pl->inflight;
   b.lo = pl->mem.lo.as<double>();
   b.lo2 = pl->mem.lo2.as<double>();
   b.s1 = pl->s1;
   b.s2 = pl->mem.s2.as<double>();
   b.s3 = pl->s3;
-  uint32_t* const words = pl->mem.words.as<uint32_t>();
-  int32_t* const flags = pl->mem.flags.as<int32_t>();
-  b.words = words;
-  b.flags = flags;
-  b.bp_flags = flags + pl->groups * kWave;
-  b.out = d_out;
-  b.out_stride = out_stride;
-  b.out_len = d_len;
-  b.sync_idx = d_sync;
-  b.edge = d_edge;
-  b.no_fuse = d_soft ? 1 : 0;
-  // AMR_SYNC_EACH_KERNEL=1: synchronise after every launch so a fault names its kernel
-  static const bool sync_each = [] {
-    const char* e = std::getenv("AMR_SYNC_EACH_KERNEL");
-    return e && e[0] == '1';
-  }();
-  auto mark = [&](int slot, int which) -> hipError_t {
-    if (sync_each && which == 1) {
-      hipError_t e = hipStreamSynchronize(st);
-      if (e != hipSuccess) {
-        static const char* names[] = {"bandpass", "lowpass_fwd", "lowpass_bwd", "lowpass_exact", "slice+sync_pack", "fec"};
-        std::fprintf(stderr, "[amr] kernel slot %s failed: %s\n", names[slot], hipGetErrorString(e));
-        return e;
-      }
-    }
-    if (!pl->timing) return hipSuccess;
-    pl->ev_used[slot] = true;
-    return hipEventRecord(pl->ev[slot][which], st);
-  };
-  if (pl->p.n_sym < 2) {
-    // modem.py:95-96, 211: fewer than two symbols -> b''
-    HIP_TRY(gate_wait(pl->gate, st));
-    HIP_TRY(hipMemsetAsync(d_len, 0, (size_t)B * 8, st));
-    HIP_TRY(hipMemsetAsync(d_sync, 0xFF, (size_t)B * 8, st));
-  } else if (layout == AMR_LAYOUT_SPLIT) {
-    if (split_strict_on(pl))
-      if (int rc = strict_prepare(pl)) return rc;
-    PskSplit sp = split_params(pl, B, 0);
-    if (int rc = ensure_split_zs(pl, sp, B)) return rc;
-    if (int rc = ensure_strict_sc(pl, sp, B)) return rc;
-    sp.zs = pl->mem.split_zs.as<double>();
-    // peaks, flags, count
-    HIP_TRY(hipMemsetAsync(pl->mem.split_peak.get(), 0, (size_t)pl->max_streams * 12 + 4, st));
-    if (sp.strict) HIP_TRY(hipMemsetAsync(sp.bnd, 0, (size_t)B * 64, st));
-    pl->last_strict = sp.strict != 0;
-    HIP_TRY(mark(AMR_T_BANDPASS, 0));
-    HIP_TRY(launch_psk_split_bp(b, pl->p, pl->bp, sp, st));
-    HIP_TRY(mark(AMR_T_BANDPASS, 1));
-    HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
-    HIP_TRY(launch_psk_split_lp(b, pl->p, pl->lp, sp, st));
-    HIP_TRY(mark(AMR_T_LOWPASS_FWD, 1));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
-    HIP_TRY(launch_psk_split_slice(b, pl->p, sp, st));
-    HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
-    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
-    // the serial row kernels over the whole batch, each exiting at once while
-    // no stream was flagged (the count on the device; no host round trip)
-    PskBuffers g = b;
-    g.gate = pl->split_count;
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 0));
-    HIP_TRY(launch_psk_bandpass(g, pl->p, pl->bp, st));
-    if (pl->lp_exact_only) {
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
-    } else {
-      HIP_TRY(launch_psk_lowpass_fwd(g, pl->p, pl->lp, st));
-      HIP_TRY(launch_psk_lowpass_bwd(g, pl->p, pl->lp, st));
-    }
-    HIP_TRY(launch_psk_lowpass_exact(g, pl->p, pl->lp, st));
-    HIP_TRY(launch_psk_slice(g, pl->p, st));
-    HIP_TRY(launch_sync_pack_gated(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, pl->split_count,
-                                   st));
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 1));
-  } else if (lane) {
-    // AMR_PSK_F32F=1 (an A/B, off by default): the float32 hand-off of f
-    // between the band-pass and the low-pass (PskBuffers::f32f, DESIGN.md
-    // §3.1) when the low-pass slices fused.  Bit-exact (margin + fix-up), and
-    // the two kernels ran 8-12 % faster in flight, but its rigorous margin
-    // flags 3.6 % of the benchmark's streams, whose groups the fix-up and K3x
-    // then redo: 13.9 vs 3.72-3.79 ms/step (profiles/r05_psk_f32f_ab.txt)
-    static const bool f32f_env = [] { const char* e = std::getenv("AMR_PSK_F32F"); return e && e[0] == '1'; }();
-    b.fpeak = reinterpret_cast<double*>(pl->mem.split_peak.as<unsigned long long>());
-    b.f32f = f32f_env && pl->p.f32_margin > 0.0 && !pl->lp_exact_only && psk_lane_fused(b, pl->p) ? 1 : 0;
-    pl->last_f32f = b.f32f != 0;
-    HIP_TRY(mark(AMR_T_BANDPASS, 0));
-    HIP_TRY(launch_psk_bandpass_lane(b, pl->p, pl->bp, st));
-    HIP_TRY(mark(AMR_T_BANDPASS, 1));
-    bool sliced = false;                        // the low-pass wrote the words itself (k_lp_lane FUSE)
-    if (pl->lp_exact_only) {
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
-    } else {
-      // forward + backward low-pass in one kernel: timed in the lowpass_fwd slot
-      HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
-      HIP_TRY(launch_psk_lowpass_lane(b, pl->p, pl->lp, st, &sliced, &pl->last_lowpass));
-      HIP_TRY(mark(AMR_T_LOWPASS_FWD, 1));
-    }
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 0));
-    // AMR_PSK_F32F_NOFIX=1: a timing-only diagnostic (flagged streams' bytes then wrong): no fix-up
-    static const bool nofix = [] { const char* e = std::getenv("AMR_PSK_F32F_NOFIX"); return e && e[0] == '1'; }();
-    if (b.f32f && !nofix) HIP_TRY(launch_psk_bandpass_fixup(b, pl->p, pl->bp, st));   // float64 f of the flagged groups
-    HIP_TRY(launch_psk_lowpass_exact(b, pl->p, pl->lp, st));
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 1));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
+  b.words = pl->mem.words.as<uint32_t>();
+  b.flags = pl->mem.flags.as<int32_t>();
+  b.bp_flags = b.flags + pl->groups * kWave;
+  b.out = c.io.out;
+  b.out_stride = c.io.out_stride;
+  b.out_len = c.io.len;
+  b.sync_idx = c.io.sync;
+  b.edge = c.edge;
+  b.no_fuse = c.soft.ptr ? 1 : 0;
+  return b;
+}
+
+// the decided words to bytes, lengths and sync indices (gate: only once a stream was flagged, run_psk_split)
+hipError_t psk_sync_pack(amr_psk_plan* pl, const DemodIo& io, const uint32_t* w, const int32_t* gate = nullptr) {
+  const PskParams& p = pl->p;
+  if (!gate) return launch_sync_pack(w, p.n_words, p.n_bits, io.B, io.out, io.out_stride, io.len, io.sync, pl->stream);
+  return launch_sync_pack_gated(w, p.n_words, p.n_bits, io.B, io.out, io.out_stride, io.len, io.sync, gate, pl->stream);
+}
+
+// modem.py:95-96, 211: fewer than two symbols -> b''
+int run_psk_empty(amr_psk_plan* pl, const PskCall& c) {
+  HIP_TRY(gate_wait(pl->gate, pl->stream));
+  HIP_TRY(hipMemsetAsync(c.io.len, 0, (size_t)c.io.B * 8, pl->stream));
+  HIP_TRY(hipMemsetAsync(c.io.sync, 0xFF, (size_t)c.io.B * 8, pl->stream));
+  return AMR_OK;
+}
+
+// The serial row kernels and sync + pack: the row layout, each stage in its
+// timing slot; or (gated) the split layout's fallback over the whole batch,
+// each kernel exiting at once while no stream was flagged (the count on the
+// device; no host round trip), untimed here: run_psk_split times the chain
+// as one, and has waited for the gather gate already.
+int run_psk_row(amr_psk_plan* pl, const PskCall& c, PskBuffers b, bool gated = false) {
+  hipStream_t st = pl->stream;
+  if (gated) b.gate = pl->split_count;
+  const auto slot = [gated](int s) { return gated ? kNoSlot : s; };
+  HIP_TRY_TIMED(*pl, slot(AMR_T_BANDPASS), launch_psk_bandpass(b, pl->p, pl->bp, st));
+  if (pl->lp_exact_only) {
+    // every stream takes the exact complex path
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b.flags, 1, (size_t)c.io.B, st));
+  } else {
+    HIP_TRY_TIMED(*pl, slot(AMR_T_LOWPASS_FWD), launch_psk_lowpass_fwd(b, pl->p, pl->lp, st));
+    HIP_TRY_TIMED(*pl, slot(AMR_T_LOWPASS_BWD), launch_psk_lowpass_bwd(b, pl->p, pl->lp, st));
+  }
+  HIP_TRY_TIMED(*pl, slot(AMR_T_LOWPASS_EXACT), launch_psk_lowpass_exact(b, pl->p, pl->lp, st));
+  return timed(*pl, slot(AMR_T_SYNC_PACK), [&]() -> int {
+    HIP_TRY(launch_psk_slice(b, pl->p, st));
+    if (!gated) HIP_TRY(gate_wait(pl->gate, st));      // the outputs: after any gather still reading them
+    HIP_TRY(psk_sync_pack(pl, c.io, b.words, b.gate));
+    if (c.soft.ptr) HIP_TRY(launch_psk_soft(b, pl->p, c.soft.ptr, c.soft.stride, st));
+    return AMR_OK;
+  });
+}
+
+int run_psk_lane(amr_psk_plan* pl, const PskCall& c, PskBuffers b) {
+  hipStream_t st = pl->stream;
+  // AMR_PSK_F32F=1 (an A/B, off by default): the float32 hand-off of f
+  // between the band-pass and the low-pass (PskBuffers::f32f, DESIGN.md
+  // §3.1) when the low-pass slices fused.  Bit-exact (margin + fix-up), and
+  // the two kernels ran 8-12 % faster in flight, but its rigorous margin
+  // flags 3.6 % of the benchmark's streams, whose groups the fix-up and K3x
+  // then redo: 13.9 vs 3.72-3.79 ms/step (profiles/r05_psk_f32f_ab.txt)
+  static const bool f32f_env = env_on("AMR_PSK_F32F");
+  // AMR_PSK_F32F_NOFIX=1: a timing-only diagnostic (flagged streams' bytes then wrong): no fix-up
+  static const bool nofix = env_on("AMR_PSK_F32F_NOFIX");
+  b.fpeak = reinterpret_cast<double*>(pl->mem.split_peak.as<unsigned long long>());
+  b.f32f = f32f_env && pl->p.f32_margin > 0.0 && !pl->lp_exact_only && psk_lane_fused(b, pl->p) ? 1 : 0;
+  pl->last_f32f = b.f32f != 0;
+  HIP_TRY_TIMED(*pl, AMR_T_BANDPASS, launch_psk_bandpass_lane(b, pl->p, pl->bp, st));
+  bool sliced = false;                        // the low-pass wrote the words itself (k_lp_lane FUSE)
+  if (pl->lp_exact_only) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b.flags, 1, (size_t)c.io.B, st));
+  } else {
+    // forward + backward low-pass in one kernel: timed in the lowpass_fwd slot
+    HIP_TRY_TIMED(*pl, AMR_T_LOWPASS_FWD, launch_psk_lowpass_lane(b, pl->p, pl->lp, st, &sliced, &pl->last_lowpass));
+  }
+  if (int rc = timed(*pl, AMR_T_LOWPASS_EXACT, [&]() -> int {
+        if (b.f32f && !nofix) HIP_TRY(launch_psk_bandpass_fixup(b, pl->p, pl->bp, st));   // float64 f of the flagged groups
+        HIP_TRY(launch_psk_lowpass_exact(b, pl->p, pl->lp, st));
+        return AMR_OK;
+      }))
+    return rc;
+  return timed(*pl, AMR_T_SYNC_PACK, [&]() -> int {
     HIP_TRY(launch_psk_slice(b, pl->p, st, sliced));   // then only the K3x streams
     HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
-    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
-    if (d_soft) HIP_TRY(launch_psk_soft(b, pl->p, d_soft, soft_stride, st));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
-  } else {
-    HIP_TRY(mark(AMR_T_BANDPASS, 0));
-    HIP_TRY(launch_psk_bandpass(b, pl->p, pl->bp, st));
-    HIP_TRY(mark(AMR_T_BANDPASS, 1));
-    if (pl->lp_exact_only) {
-      // every stream takes the exact complex path
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)B, st));
-    } else {
-      HIP_TRY(mark(AMR_T_LOWPASS_FWD, 0));
-      HIP_TRY(launch_psk_lowpass_fwd(b, pl->p, pl->lp, st));
-      HIP_TRY(mark(AMR_T_LOWPASS_FWD, 1));
-      HIP_TRY(mark(AMR_T_LOWPASS_BWD, 0));
-      HIP_TRY(launch_psk_lowpass_bwd(b, pl->p, pl->lp, st));
-      HIP_TRY(mark(AMR_T_LOWPASS_BWD, 1));
+    HIP_TRY(psk_sync_pack(pl, c.io, b.words));
+    if (c.soft.ptr) HIP_TRY(launch_psk_soft(b, pl->p, c.soft.ptr, c.soft.stride, st));
+    return AMR_OK;
+  });
+}
+
+int run_psk_split(amr_psk_plan* pl, const PskCall& c, const PskBuffers& b) {
+  hipStream_t st = pl->stream;
+  if (split_strict_on(pl))
+    if (int rc = strict_prepare(pl)) return rc;
+  PskSplit sp;
+  if (int rc = split_begin(pl, c.io.B, 0, false, &sp)) return rc;
+  pl->last_strict = sp.strict != 0;
+  HIP_TRY_TIMED(*pl, AMR_T_BANDPASS, launch_psk_split_bp(b, pl->p, pl->bp, sp, st));
+  HIP_TRY_TIMED(*pl, AMR_T_LOWPASS_FWD, launch_psk_split_lp(b, pl->p, pl->lp, sp, st));
+  if (int rc = timed(*pl, AMR_T_SYNC_PACK, [&]() -> int {
+        HIP_TRY(launch_psk_split_slice(b, pl->p, sp, st));
+        HIP_TRY(gate_wait(pl->gate, st));              // the outputs: after any gather still reading them
+        HIP_TRY(psk_sync_pack(pl, c.io, b.words));
+        return AMR_OK;
+      }))
+    return rc;
+  return timed(*pl, AMR_T_LOWPASS_EXACT, [&] { return run_psk_row(pl, c, b, true); });
+}
+
+// Launch the whole PSK pipeline on plan->stream.  Caller holds plan->mu.
+int run_psk(amr_psk_plan* pl, const PskCall& c) {
+  const DemodIo& io = c.io;
+  if (int rc = check_demod_args(pl, io, ArgOrder::device)) return rc;
+  core_clear_used(*pl);
+  pl->last_exact = io.B;
+  if (io.B == 0) return AMR_OK;
+  return timed(*pl, AMR_T_LAUNCH, [&]() -> int {
+    const int layout = pick_layout(pl, io.B, c.soft.ptr != nullptr);
+    const bool lane = layout == AMR_LAYOUT_LANE;
+    pl->last_layout = layout;
+    pl->last_lowpass = -1;
+    if (pl->p.n_sym >= 2) {
+      // the sizes this layout's kernels assume (the row layout's full-length
+      // intermediates are allocated on its first call; the time-split layout
+      // keeps its passes' outputs in the same buffers and runs the row kernels
+      // behind them); a plan whose earlier grow failed re-tries here and fails
+      // cleanly if it still cannot
+      const int64_t b1 = kFrontSlack * 8 + (lane ? lane_s1_bytes(pl) : row_s1_bytes(pl));
+      const int64_t b3 = kFrontSlack * 8 + (lane ? lane_s3_bytes(pl) : row_s3_bytes(pl));
+      if (int rc = ensure_scratch(pl, b1, b3)) return rc;
     }
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 0));
-    HIP_TRY(launch_psk_lowpass_exact(b, pl->p, pl->lp, st));
-    HIP_TRY(mark(AMR_T_LOWPASS_EXACT, 1));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 0));
-    HIP_TRY(launch_psk_slice(b, pl->p, st));
-    HIP_TRY(gate_wait(pl->gate, st));
-    HIP_TRY(launch_sync_pack(words, pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync, st));
-    if (d_soft) HIP_TRY(launch_psk_soft(b, pl->p, d_soft, soft_stride, st));
-    HIP_TRY(mark(AMR_T_SYNC_PACK, 1));
-  }
-  if (d_fec) {
+    const PskBuffers b = psk_buffers(pl, c);
+    if (int rc = pl->p.n_sym < 2                ? run_psk_empty(pl, c)
+                 : layout == AMR_LAYOUT_SPLIT ? run_psk_split(pl, c, b)
+                 : lane                       ? run_psk_lane(pl, c, b)
+                                              : run_psk_row(pl, c, b))
+      return rc;
+    if (!c.fec.out) return AMR_OK;
     const uint32_t *tab = nullptr, *x2n = nullptr;
-    int rc = device_crc(pl->device, &tab, &x2n);
-    if (rc) return rc;
-    HIP_TRY(mark(AMR_T_FEC, 0));
-    HIP_TRY(launch_fec_decode(d_out, out_stride, d_len, B, d_fec, fec_stride, d_fec_len, d_crc, tab, x2n, st));
-    HIP_TRY(mark(AMR_T_FEC, 1));
-  }
-  if (pl->timing) HIP_TRY(hipEventRecord(pl->ev[AMR_T_LAUNCH][1], st));
-  return AMR_OK;
+    if (int rc = device_crc(pl->device, &tab, &x2n)) return rc;
+    return timed(*pl, AMR_T_FEC, [&]() -> int {
+      HIP_TRY(launch_fec_decode(io.out, io.out_stride, io.len, io.B, c.fec.out, c.fec.stride, c.fec.len, c.fec.crc, tab,
+                                x2n, pl->stream));
+      return AMR_OK;
+    });
+  });
 }
 
 // the time-split passes alone (KS1-KS4) with chunk length L: the symbol
@@ -1283,30 +1233,12 @@ int run_psk(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_s
 int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, int64_t L,
                         double* ebound) {
   if (int rc = ensure_scratch(pl, kFrontSlack * 8 + row_s1_bytes(pl), kFrontSlack * 8 + row_s3_bytes(pl))) return rc;
-  PskBuffers b{};
-  b.x = d_x;
-  b.x_stride = x_stride;
-  b.dtype = dtype;
-  b.n_streams = B;
-  b.lo = pl->mem.lo.as<double>();
-  b.lo2 = pl->mem.lo2.as<double>();
-  const int saved = pl->strict_mode;
-  if (ebound) {
-    pl->strict_mode = 1;
-    if (int rc = strict_prepare(pl)) { pl->strict_mode = saved; return rc; }
-  }
-  PskSplit sp = split_params(pl, B, L);
-  pl->strict_mode = saved;
-  if (ebound && !sp.strict) return fail(AMR_E_INVALID, "no strict bound for this plan (no convolution starts or design)");
-  if (int rc = ensure_split_zs(pl, sp, B)) return rc;
-  if (int rc = ensure_strict_sc(pl, sp, B)) return rc;
-  sp.zs = pl->mem.split_zs.as<double>();
-  HIP_TRY(hipMemsetAsync(pl->mem.split_peak.get(), 0, (size_t)pl->max_streams * 12 + 4, pl->stream));
-  if (sp.strict) HIP_TRY(hipMemsetAsync(sp.bnd, 0, (size_t)B * 64, pl->stream));
+  const PskBuffers b = psk_buffers(pl, PskCall{{d_x, dtype, B, x_stride}});
+  PskSplit sp;
+  if (int rc = split_begin(pl, B, L, ebound != nullptr, &sp)) return rc;
   HIP_TRY(launch_psk_split_bp(b, pl->p, pl->bp, sp, pl->stream));
   HIP_TRY(launch_psk_split_lp(b, pl->p, pl->lp, sp, pl->stream));
   if (ebound) {
-    b.words = pl->mem.words.as<uint32_t>();
     HIP_TRY(launch_psk_split_slice(b, pl->p, sp, pl->stream));
     // e(k) and the scalars of every stream, packed [B][S + 4]
     const int64_t S = pl->p.n_sym;
@@ -1316,6 +1248,65 @@ int run_psk_split_front(amr_psk_plan* pl, const void* d_x, int dtype, int64_t B,
   return AMR_OK;
 }
 
+// the host entries' staging: the input at max_streams x n x 8 B (a grow waits
+// for the stream: queued work may still read the old block) and the output
+// group, whole or not at all
+int psk_host_staging(amr_psk_plan* pl) {
+  const int64_t ms = pl->max_streams;
+  HIP_TRY(pl->mem.d_x.reserve(ms * pl->p.n * 8, pl->stream));
+  // (the inner parentheses keep the braces' commas from splitting the macro's argument)
+  HIP_TRY((reserve_all({{pl->mem.d_out, ms * pl->out_cap}, {pl->mem.d_len, ms * 8}, {pl->mem.d_sync, ms * 8}},
+                       pl->stream)));
+  return AMR_OK;
+}
+
+// A host entry (plan_core.h host_round_trip), blocking or queued.  edges: the
+// raw-integer capture's table, staged in d_edge.  soft: non-null, the soft
+// values too (amr_psk_demod_soft_host), through a staging block of this
+// call's own (hipFree, when the call returns, waits for the device).
+int psk_demod_host(amr_psk_plan* plan, const char* who, const DemodIo& h, Copy how, const double* edges = nullptr,
+                   int8_t* soft = nullptr, int64_t soft_stride = 0) {
+  DevBuf d_soft;
+  int64_t sv = 0;   // its row: every value the kernel can write, 8 * out_len <= n_bits
+  const int rc = host_round_trip(plan, who, h, how, [&]() -> int {
+    amr_psk_plan::Mem& m = plan->mem;
+    const int64_t n = plan->p.n, es = dtype_size(h.dtype);
+    if (int rc = psk_host_staging(plan)) return rc;
+    if (int rc = upload_batch(how, m.d_x.get(), h.x, n * es, h.x_stride * es, h.B, plan->stream)) return rc;
+    PskCall c{{m.d_x.get(), h.dtype, h.B, n, m.d_out.as<uint8_t>(), plan->out_cap, m.d_len.as<int64_t>(),
+               m.d_sync.as<int64_t>()}};
+    if (edges) {
+      const int64_t row = 2 * plan->p.pad1 * 8;
+      HIP_TRY(m.d_edge.reserve(plan->max_streams * row, plan->stream));
+      HIP_TRY(hipMemcpyAsync(m.d_edge.get(), edges, (size_t)(h.B * row), hipMemcpyHostToDevice, plan->stream));
+      c.edge = m.d_edge.as<double>();
+    }
+    std::optional<LastCall> keep;
+    if (soft) {
+      sv = std::max<int64_t>(plan->p.n_bits, 1);
+      HIP_TRY(d_soft.reserve(h.B * sv, nullptr));
+      c.soft = {d_soft.as<int8_t>(), sv};
+      keep.emplace(plan);
+    }
+    return run_psk(plan, c);
+  });
+  if (rc || !soft || h.B == 0) return rc;
+  // only the values of the stream's bytes reach the caller's row
+  std::vector<int8_t> tmp((size_t)(h.B * sv));
+  HIP_TRY(hipMemcpy(tmp.data(), d_soft.get(), tmp.size(), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < h.B; ++i)
+    std::memcpy(soft + i * soft_stride, tmp.data() + i * sv, (size_t)std::min(8 * h.len[i], soft_stride));
+  return AMR_OK;
+}
+
+// a device entry: the plan's lock and device, then the launch
+int psk_demod_device(amr_psk_plan* plan, const PskCall& c) {
+  std::lock_guard<std::mutex> lk(plan->mu);
+  HIP_TRY(hipSetDevice(plan->device));
+  std::optional<LastCall> keep;
+  if (c.soft.ptr) keep.emplace(plan);
+  return run_psk(plan, c);
+}
 }  // namespace
 
 extern "C" {
@@ -1325,10 +1316,8 @@ int amr_psk_demod_device(amr_psk_plan* plan, const void* d_x, int dtype, int64_t
   if (!plan || (!d_x && n_streams) || (!d_out && n_streams) || (!d_out_len && n_streams) ||
       (!d_sync_idx && n_streams))
     return fail(AMR_E_INVALID, "amr_psk_demod_device: NULL argument");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  return run_psk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, nullptr, 0,
-                 nullptr, nullptr);
+  PskCall c{{d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}};
+  return psk_demod_device(plan, c);
 }
 
 int amr_psk_demod_fec_device(amr_psk_plan* plan, const void* d_x, int dtype, int64_t n_streams,
@@ -1337,10 +1326,9 @@ int amr_psk_demod_fec_device(amr_psk_plan* plan, const void* d_x, int dtype, int
                              int32_t* d_crc_ok) {
   if (!plan || !d_fec || !d_fec_len || !d_crc_ok) return fail(AMR_E_INVALID, "NULL argument");
   if (fec_stride < out_stride) return fail(AMR_E_INVALID, "fec_stride < out_stride");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  return run_psk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, d_fec,
-                 fec_stride, d_fec_len, d_crc_ok);
+  PskCall c{{d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}};
+  c.fec = {d_fec, fec_stride, d_fec_len, d_crc_ok};
+  return psk_demod_device(plan, c);
 }
 
 int amr_psk_demod_device_edges(amr_psk_plan* plan, const void* d_x, int dtype, int64_t n_streams, int64_t x_stride,
@@ -1348,22 +1336,23 @@ int amr_psk_demod_device_edges(amr_psk_plan* plan, const void* d_x, int dtype, i
                                int64_t* d_sync_idx) {
   if (!plan || (n_streams && (!d_x || !d_edges || !d_out || !d_out_len || !d_sync_idx)))
     return fail(AMR_E_INVALID, "amr_psk_demod_device_edges: NULL argument");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  return run_psk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, nullptr, 0,
-                 nullptr, nullptr, d_edges);
+  PskCall c{{d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}};
+  c.edge = d_edges;
+  return psk_demod_device(plan, c);
 }
 
 int amr_psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
                        uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
-  return psk_demod_host(plan, x, dtype, B, x_stride, nullptr, out, out_stride, out_len, sync_idx);
+  return psk_demod_host(plan, "amr_psk_demod_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                        Copy::sync);
 }
 
 int amr_psk_demod_host_edges(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
                              const double* edges, uint8_t* out, int64_t out_stride, int64_t* out_len,
                              int64_t* sync_idx) {
   if (B && !edges) return fail(AMR_E_INVALID, "amr_psk_demod_host_edges: NULL edges");
-  return psk_demod_host(plan, x, dtype, B, x_stride, edges, out, out_stride, out_len, sync_idx);
+  return psk_demod_host(plan, "amr_psk_demod_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                        Copy::sync, edges);
 }
 
 // ---- soft-decision output (K4s) --------------------------------
@@ -1376,11 +1365,10 @@ int amr_psk_demod_soft_device(amr_psk_plan* plan, const void* d_x, int dtype, in
     return fail(AMR_E_INVALID, "amr_psk_demod_soft_device: NULL argument");
   if (soft_stride < 8 * plan->out_cap)
     return fail(AMR_E_INVALID, "amr_psk_demod_soft_device: soft_stride < 8 * amr_psk_plan_out_capacity()");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  LastCall keep(plan);
-  return run_psk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, nullptr, 0, nullptr,
-                 nullptr, d_edges, d_soft, soft_stride);
+  PskCall c{{d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}};
+  c.edge = d_edges;
+  c.soft = {d_soft, soft_stride};
+  return psk_demod_device(plan, c);
 }
 
 int amr_psk_demod_soft_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, uint8_t* out,
@@ -1391,83 +1379,9 @@ int amr_psk_demod_soft_host(amr_psk_plan* plan, const void* x, int dtype, int64_
   if (!plan || (B && !soft)) return fail(AMR_E_INVALID, "amr_psk_demod_soft_host: NULL argument");
   if (soft_stride < 8 * plan->out_cap)
     return fail(AMR_E_INVALID, "amr_psk_demod_soft_host: soft_stride < 8 * amr_psk_plan_out_capacity()");
-  return psk_demod_host(plan, x, dtype, B, x_stride, edges, out, out_stride, out_len, sync_idx, soft, soft_stride);
+  return psk_demod_host(plan, "amr_psk_demod_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                        Copy::sync, edges, soft, soft_stride);
 }
-
-}  // extern "C"
-
-namespace {
-// the host entries' staging: the input at max_streams x n x 8 B (a grow waits
-// for the stream: queued work may still read the old block) and the output
-// group, whole or not at all
-int psk_host_staging(amr_psk_plan* pl) {
-  const int64_t ms = pl->max_streams;
-  HIP_TRY(pl->mem.d_x.reserve(ms * pl->p.n * 8, pl->stream));
-  // (the inner parentheses keep the braces' commas from splitting the macro's argument)
-  HIP_TRY((reserve_all({{pl->mem.d_out, ms * pl->out_cap}, {pl->mem.d_len, ms * 8}, {pl->mem.d_sync, ms * 8}},
-                       pl->stream)));
-  return AMR_OK;
-}
-// soft: non-null, the soft values too (amr_psk_demod_soft_host), through a staging block of this call's own
-int psk_demod_host(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
-                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx, int8_t* soft,
-                   int64_t soft_stride) {
-  if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
-    return fail(AMR_E_INVALID, "amr_psk_demod_host: NULL argument");
-  const int64_t es = dtype_size(dtype);
-  if (!es) return fail(AMR_E_INVALID, "unknown dtype");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  // the same argument contract as the device entry point (run_psk), checked
-  // before any copy: a short out_stride would cut rows while out_len still
-  // reports their full length
-  if (x_stride < plan->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < plan->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  if (B == 0) return AMR_OK;
-  const int64_t n = plan->p.n;
-  const int64_t cap = plan->out_cap;
-  amr_psk_plan::Mem& m = plan->mem;
-  if (int rc = psk_host_staging(plan)) return rc;
-  int rc = copy_batch_h2d(m.d_x.get(), x, n * es, x_stride * es, B, plan->stream);
-  if (rc) return rc;
-  const double* d_edge = nullptr;
-  if (edges) {
-    const int64_t eb = B * 2 * plan->p.pad1 * 8;
-    HIP_TRY(m.d_edge.reserve(plan->max_streams * 2 * plan->p.pad1 * 8, plan->stream));
-    HIP_TRY(hipMemcpyAsync(m.d_edge.get(), edges, (size_t)eb, hipMemcpyHostToDevice, plan->stream));
-    d_edge = m.d_edge.as<double>();
-  }
-  // the soft values' staging is this call's own: every row the kernel can write, 8 * out_len <= n_bits values
-  // (hipFree, when the call returns, waits for the device)
-  const int64_t sv = std::max<int64_t>(plan->p.n_bits, 1);
-  DevBuf d_soft;
-  if (soft) {
-    HIP_TRY(d_soft.reserve(B * sv, nullptr));
-    LastCall keep(plan);
-    rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
-                 m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge, d_soft.as<int8_t>(), sv);
-  } else {
-    rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
-                 m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr, d_edge);
-  }
-  if (rc) return rc;
-  rc = copy_batch_d2h(out, out_stride, m.d_out.get(), cap, out_stride < cap ? out_stride : cap, B, plan->stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out_len, m.d_len.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipMemcpyAsync(sync_idx, m.d_sync.get(), (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  if (soft) {                                      // only the values of the stream's bytes reach the caller's row
-    std::vector<int8_t> tmp((size_t)(B * sv));
-    HIP_TRY(hipMemcpy(tmp.data(), d_soft.get(), tmp.size(), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < B; ++i)
-      std::memcpy(soft + i * soft_stride, tmp.data() + i * sv, (size_t)std::min(8 * out_len[i], soft_stride));
-  }
-  return AMR_OK;
-}
-}  // namespace
-
-extern "C" {
 
 // Queued host entry: upload, demod and download on the plan's stream, no
 // wait.  With two or more plans used in turn, batch k+1's upload (PCIe) runs
@@ -1477,37 +1391,8 @@ extern "C" {
 // (amr_host_register) make the copies truly asynchronous.
 int amr_psk_demod_host_async(amr_psk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
                              uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
-  if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
-    return fail(AMR_E_INVALID, "amr_psk_demod_host_async: NULL argument");
-  const int64_t es = dtype_size(dtype);
-  if (!es) return fail(AMR_E_INVALID, "unknown dtype");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  if (x_stride < plan->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < plan->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  if (B == 0) return AMR_OK;
-  const int64_t n = plan->p.n;
-  const int64_t cap = plan->out_cap;
-  amr_psk_plan::Mem& m = plan->mem;
-  if (int rc = psk_host_staging(plan)) return rc;
-  hipStream_t st = plan->stream;
-  if (x_stride == n)
-    HIP_TRY(hipMemcpyAsync(m.d_x.get(), x, (size_t)(B * n * es), hipMemcpyHostToDevice, st));
-  else
-    HIP_TRY(hipMemcpy2DAsync(m.d_x.get(), (size_t)(n * es), x, (size_t)(x_stride * es), (size_t)(n * es), (size_t)B,
-                             hipMemcpyHostToDevice, st));
-  if (int rc = run_psk(plan, m.d_x.get(), dtype, B, n, m.d_out.as<uint8_t>(), cap, m.d_len.as<int64_t>(),
-                       m.d_sync.as<int64_t>(), nullptr, 0, nullptr, nullptr))
-    return rc;
-  if (out_stride == cap)
-    HIP_TRY(hipMemcpyAsync(out, m.d_out.get(), (size_t)(B * cap), hipMemcpyDeviceToHost, st));
-  else
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, m.d_out.get(), (size_t)cap, (size_t)std::min(out_stride, cap),
-                             (size_t)B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_len, m.d_len.get(), (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sync_idx, m.d_sync.get(), (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  return AMR_OK;
+  return psk_demod_host(plan, "amr_psk_demod_host_async",
+                        {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx}, Copy::async);
 }
 
 int amr_host_alloc(void** p, int64_t bytes) {
@@ -1645,16 +1530,9 @@ int amr_frame_parse_device(amr_psk_plan* plan, const uint8_t* d_in, int64_t in_s
   if (n == 0) return AMR_OK;
   int dev = 0;
   hipStream_t st = nullptr;
-  if (plan) {
-    dev = plan->device;
-    st = plan->stream;
-    HIP_TRY(hipSetDevice(dev));
-  } else {
-    HIP_TRY(hipGetDevice(&dev));
-  }
+  if (int rc = plan_stream(plan, &dev, &st)) return rc;
   const uint32_t *tab = nullptr, *x2n = nullptr;
-  int rc = device_crc(dev, &tab, &x2n);
-  if (rc) return rc;
+  if (int rc = device_crc(dev, &tab, &x2n)) return rc;
   HIP_TRY(launch_frame_parse(d_in, in_stride, d_in_len, n, max_cands, d_n_cands, d_recs, tab, x2n, st));
   return AMR_OK;
 }

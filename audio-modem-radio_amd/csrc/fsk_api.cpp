@@ -26,6 +26,7 @@
 #include "fsk_exact.h"
 #include "fft.h"
 #include "iir_design.h"
+#include "plan_core.h"
 #include "split_strict.h"
 
 namespace amr {
@@ -315,10 +316,7 @@ hipError_t fft_hilbert(const FftPlan& f, const double2* in, double2* u, double2*
 
 }  // namespace
 
-struct amr_fsk_plan {
-  std::mutex mu;
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct amr_fsk_plan : PlanCore<AMR_TF_COUNT> {
   FskParams p{};
   FskIir f{};
   FftPlan fft{};
@@ -427,11 +425,6 @@ struct amr_fsk_plan {
   int strict_mode = -1;        // amr_fsk_plan_set_split_strict: 1 on, 0 off, -1 the default
   bool strict_designed = false, strict_ok = false, last_strict = false;
   StrictDesign sdes[2];
-  GatherGate gate;             // an all-gather still reading this plan's outputs
-  // timing
-  bool timing = false;
-  hipEvent_t ev[AMR_TF_COUNT][2]{};
-  bool ev_used[AMR_TF_COUNT]{};
 };
 
 namespace {
@@ -463,9 +456,7 @@ void fsk_plan_free(amr_fsk_plan* pl) {
   if (pl->xcount_host) (void)hipHostFree(pl->xcount_host);
   pl->mem = amr_fsk_plan::Mem{};                 // frees every device buffer
   pl->fft.mem = FftPlan::Mem{};
-  for (auto& e : pl->ev)
-    for (auto& h : e)
-      if (h) (void)hipEventDestroy(h);
+  core_destroy_events(*pl);
   if (pl->ev_f2) (void)hipEventDestroy(pl->ev_f2);
   if (pl->ev_x) (void)hipEventDestroy(pl->ev_x);
   if (pl->xstream) (void)hipStreamDestroy(pl->xstream);
@@ -476,12 +467,6 @@ void fsk_plan_free(amr_fsk_plan* pl) {
 // this call keeps z whole through F2 (dd allocated: see amr_fsk_plan::dd;
 // a split call's z is not scipy's, so the exact path re-runs F1 instead)
 bool keeps_z(const amr_fsk_plan* pl) { return pl->keep_z && pl->mem.dd && !pl->split_now; }
-
-hipError_t mark_fsk(amr_fsk_plan* pl, int slot, int which, hipStream_t st = nullptr) {
-  if (!pl->timing) return hipSuccess;
-  pl->ev_used[slot] = true;
-  return hipEventRecord(pl->ev[slot][which], st ? st : pl->stream);
-}
 
 // F1 over the B streams of x -> z (and, with the exact path on, each
 // stream's ambiguity scale; the flag words cleared).  Caller holds mu.
@@ -501,17 +486,14 @@ constexpr int64_t kFskSplitConvChunks = 3072;
 // the split F1's strict margin by default (AMR_FSK_SPLIT_STRICT=0 / 1 overrides)
 constexpr int kFskStrictDefault = 1;
 bool fsk_split_conv_on(const amr_fsk_plan* pl) {
-  static const bool env = [] { const char* e = std::getenv("AMR_FSK_SPLIT_CONV"); return !(e && e[0] == '0'); }();
+  static const bool env = env_not_off("AMR_FSK_SPLIT_CONV");
   return env && pl->split_ok && !pl->split_tab_host.empty();
 }
 // STRICT: AMR_FSK_SPLIT_STRICT=0 / 1 sets the default, amr_fsk_plan_set_split_strict
 // a plan's; the bound covers the convolution starts only
 bool fsk_split_strict_on(const amr_fsk_plan* pl) {
-  static const int env = [] {
-    const char* e = std::getenv("AMR_FSK_SPLIT_STRICT");
-    return e ? (e[0] == '1' ? 1 : 0) : kFskStrictDefault;
-  }();
-  const bool want = pl->strict_mode >= 0 ? pl->strict_mode == 1 : env == 1;
+  static const int env = env_tri("AMR_FSK_SPLIT_STRICT");   // unset: kFskStrictDefault
+  const bool want = pl->strict_mode >= 0 ? pl->strict_mode == 1 : (env < 0 ? kFskStrictDefault : env) == 1;
   return want && fsk_split_conv_on(pl);
 }
 FskSplit fsk_split_params(amr_fsk_plan* pl, int64_t B, int64_t L) {
@@ -547,10 +529,7 @@ int fsk_strict_prepare(amr_fsk_plan* pl) {
   const int64_t w = pl->split_w;
   bool ok = true;
   for (int t = 0; t < 2 && ok; ++t) {
-    Iir fi{};
-    fi.nt = nt;
-    for (int i = 0; i < nt; ++i) { fi.b[i] = pl->f.b[t][i]; fi.a[i] = pl->f.a[t][i]; }
-    for (int i = 0; i < nt - 1; ++i) fi.zi[i] = pl->f.zi[t][i];
+    const Iir fi = make_iir(pl->f.b[t], pl->f.a[t], pl->f.zi[t], nt);
     StrictDesign& d = pl->sdes[t];
     ok = strict_design_bp(fi, pl->split_tab_host.data() + (size_t)t * w * 6,
                           pl->split_tab_host.data() + (size_t)(2 * w + t * (w + 1)) * 6, w, d,
@@ -609,7 +588,7 @@ int ensure_split_buffers(amr_fsk_plan* pl, int64_t B) {
 // does this call run the split F1?  Only with the exact path on (it is what
 // makes the split's decisions exact)
 bool use_split(const amr_fsk_plan* pl, int64_t B) {
-  static const bool env_off = [] { const char* e = std::getenv("AMR_FSK_SPLIT"); return e && e[0] == '0'; }();
+  static const bool env_off = !env_not_off("AMR_FSK_SPLIT");
   if (!pl->split_ok || !pl->exact_on || pl->exact_mode == 0 || pl->p.n_bits == 0 || B < 1 || B > 65535) return false;
   if (pl->split_mode == AMR_FSK_LAYOUT_SPLIT) return true;
   return pl->split_mode == AMR_FSK_LAYOUT_AUTO && !env_off && B <= kFskSplitMaxStreams;
@@ -649,18 +628,13 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
     env.amb = pl->mem.amb.as<double>();
     env.xflags = pl->mem.xflags.as<uint32_t>();
   }
-  // one timing slot for the whole Hilbert filter (column, middle and final passes)
-  HIP_TRY(mark_fsk(pl, AMR_TF_HILBERT, 0));
   if (pl->p.lc.on) {
     if (env_out) return fail(AMR_E_INVALID, "live-column plan: envelopes go through a natural-layout plan");
     // AMR_FSK_SUBBATCH=S (an A/B experiment): the three
     // passes per sub-batch of S streams (a multiple of 32: the flag words),
     // so a sub-batch's intermediates could stay in the Infinity Cache
-    static const int64_t sub = [] {
-      const char* e = std::getenv("AMR_FSK_SUBBATCH");
-      const int64_t v = e ? atoll(e) : 0;
-      return v >= 32 ? v / 32 * 32 : 0;
-    }();
+    // (rounded down to a multiple of 32; below 32: off)
+    static const int64_t sub = env_int("AMR_FSK_SUBBATCH", 32, std::numeric_limits<int64_t>::max(), 0) / 32 * 32;
     const LiveCols& lc = pl->p.lc;
     const int64_t step = sub > 0 ? sub : B;
     for (int64_t b0 = 0; b0 < B; b0 += step) {
@@ -679,7 +653,6 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
     HIP_TRY(fft_hilbert(pl->fft, pl->mem.z.as<double2>(), pl->mem.u.as<double2>(), pl->mem.v.as<double2>(), B, env,
                         pl->stream));
   }
-  HIP_TRY(mark_fsk(pl, AMR_TF_HILBERT, 1));
   return AMR_OK;
 }
 
@@ -688,7 +661,7 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
 // E3 only, E2 skipped).  Either way F3 then takes every stream's bits from the
 // fast path (run_fsk_back), not from an xbits buffer E2 / E3 never filled.
 int exact_launch_mode() {
-  static const int launch = [] { const char* e = std::getenv("AMR_FSK_EXACT_LAUNCH"); return e ? atoi(e) : 1; }();
+  static const int launch = (int)env_int("AMR_FSK_EXACT_LAUNCH", INT32_MIN, INT32_MAX, 1);
   return launch;
 }
 
@@ -714,9 +687,9 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
   X.xbits = pl->mem.xbits.as<uint8_t>();
   X.fuse = (int)pf_fuse_on();
   X.lean = X.fuse && pl->x_lean;
-  static const int xcd_pair = [] { const char* e = std::getenv("AMR_FSK_XCDPAIR"); return !(e && e[0] == '0'); }();
+  static const int xcd_pair = env_not_off("AMR_FSK_XCDPAIR");
   X.xcd_pair = xcd_pair;
-  static const int live_only = [] { const char* e = std::getenv("AMR_FSK_LIVEONLY"); return !(e && e[0] == '0'); }();
+  static const int live_only = env_not_off("AMR_FSK_LIVEONLY");
   X.live_only = live_only;
   X.count_host = pl->xcount_dev;
   if (pl->xstream && !pl->count_sync) {
@@ -735,32 +708,34 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
     HIP_TRY(hipStreamWaitEvent(pl->xstream, pl->ev_f2, 0));
     st = pl->xstream;
   }
-  HIP_TRY(mark_fsk(pl, AMR_TF_EXACT, 0, st));
-  pl->ran_exact = true;
-  HIP_TRY(launch_fsk_exact_list(B, X, st));
-  if (pl->count_sync) {
-    int32_t c = 0;
-    HIP_TRY(hipMemcpyAsync(&c, X.count, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c == 0) {                            // nothing flagged: F3 takes every stream's fast-path bits
-      pl->ran_exact = false;
-      *pl->xcount_host = 0;
-      HIP_TRY(mark_fsk(pl, AMR_TF_EXACT, 1, st));
-      return AMR_OK;
+  // the slot on the stream the exact path runs on
+  const int rc = timed(*pl, AMR_TF_EXACT, [&]() -> int {
+    pl->ran_exact = true;
+    HIP_TRY(launch_fsk_exact_list(B, X, st));
+    if (pl->count_sync) {
+      int32_t c = 0;
+      HIP_TRY(hipMemcpyAsync(&c, X.count, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (c == 0) {                            // nothing flagged: F3 takes every stream's fast-path bits
+        pl->ran_exact = false;
+        *pl->xcount_host = 0;
+        return AMR_OK;
+      }
+      X.count_hint = c;
     }
-    X.count_hint = c;
-  }
-  if (!X.live) {
-    // E1: F1 again over the flagged streams only (list mode), natural z layout
-    FskParams p1 = pl->p;
-    p1.amb = nullptr;
-    p1.lc = LiveCols{};
-    p1.xlist = X.list;
-    p1.xcount = X.count;
-    HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, pl->mem.u.as<double>(), pl->mem.z.as<double2>(), p1, pl->f, st));
-  }
-  HIP_TRY(launch_fsk_exact_env(B, pl->p, X, st, launch != 2));
-  HIP_TRY(mark_fsk(pl, AMR_TF_EXACT, 1, st));
+    if (!X.live) {
+      // E1: F1 again over the flagged streams only (list mode), natural z layout
+      FskParams p1 = pl->p;
+      p1.amb = nullptr;
+      p1.lc = LiveCols{};
+      p1.xlist = X.list;
+      p1.xcount = X.count;
+      HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, pl->mem.u.as<double>(), pl->mem.z.as<double2>(), p1, pl->f, st));
+    }
+    HIP_TRY(launch_fsk_exact_env(B, pl->p, X, st, launch != 2));
+    return AMR_OK;
+  }, st);
+  if (rc) return rc;
   if (xs) {
     HIP_TRY(hipEventRecord(pl->ev_x, pl->xstream));
     HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_x, 0));
@@ -771,20 +746,11 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
 // F1, F2 (and the exact path) on a device-resident batch: x -> cmp (or the envelopes).  Caller holds mu.
 int run_fsk_front(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, bool env_out) {
   if (env_out) pl->split_now = false;        // the envelopes themselves: scipy's F1
-  HIP_TRY(mark_fsk(pl, AMR_TF_BANDPASS, 0));
-  if (int rc = run_fsk_f1(pl, d_x, dtype, B, x_stride, !env_out)) return rc;
-  HIP_TRY(mark_fsk(pl, AMR_TF_BANDPASS, 1));
-  if (int rc = run_fsk_f2(pl, B, env_out)) return rc;
+  if (int rc = timed(*pl, AMR_TF_BANDPASS, [&] { return run_fsk_f1(pl, d_x, dtype, B, x_stride, !env_out); })) return rc;
+  // one timing slot for the whole Hilbert filter (column, middle and final passes)
+  if (int rc = timed(*pl, AMR_TF_HILBERT, [&] { return run_fsk_f2(pl, B, env_out); })) return rc;
   if (env_out) return AMR_OK;
   return run_fsk_exact(pl, d_x, dtype, B, x_stride);
-}
-
-int check_fsk_args(amr_fsk_plan* pl, int dtype, int64_t B, int64_t x_stride, int64_t out_stride) {
-  if (B < 0 || B > pl->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  if (dtype_size(dtype) == 0) return fail(AMR_E_INVALID, "unknown dtype");
-  if (x_stride < pl->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < pl->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  return AMR_OK;
 }
 
 // no decision window (sps // 4 == 0): empty bit string -> b''   (modem.py:320-323)
@@ -796,20 +762,21 @@ int fsk_empty_outputs(amr_fsk_plan* pl, int64_t B, int64_t* d_len, int64_t* d_sy
 }
 
 // F3: compare bits -> decided words -> sync + pack.  Caller holds mu.
-int run_fsk_back(amr_fsk_plan* pl, int64_t B, uint8_t* d_out, int64_t out_stride, int64_t* d_len, int64_t* d_sync) {
+int run_fsk_back(amr_fsk_plan* pl, const DemodIo& io) {
+  const int64_t B = io.B;
   hipStream_t st = pl->stream;
-  HIP_TRY(mark_fsk(pl, AMR_TF_DECIDE, 0));
   // a flagged stream's bits come from xbits only when this call's E0-E3 wrote
   // them (exact mode 0 leaves the flag words of an earlier call untouched;
   // the diagnostic launch modes leave xbits unwritten)
   FskParams p = pl->p;
   if (!pl->ran_exact || exact_launch_mode() != 1) p.xflags = nullptr;
-  HIP_TRY(launch_fsk_decide(pl->mem.cmp.as<uint8_t>(), pl->mem.words.as<uint32_t>(), B, p, st));
-  HIP_TRY(gate_wait(pl->gate, st));             // the outputs: after any gather still reading them
-  HIP_TRY(launch_sync_pack(pl->mem.words.as<uint32_t>(), pl->p.n_words, pl->p.n_bits, B, d_out, out_stride, d_len, d_sync,
-                           st));
-  HIP_TRY(mark_fsk(pl, AMR_TF_DECIDE, 1));
-  return AMR_OK;
+  return timed(*pl, AMR_TF_DECIDE, [&]() -> int {
+    HIP_TRY(launch_fsk_decide(pl->mem.cmp.as<uint8_t>(), pl->mem.words.as<uint32_t>(), B, p, st));
+    HIP_TRY(gate_wait(pl->gate, st));             // the outputs: after any gather still reading them
+    HIP_TRY(launch_sync_pack(pl->mem.words.as<uint32_t>(), pl->p.n_words, pl->p.n_bits, B, io.out, io.out_stride, io.len,
+                             io.sync, st));
+    return AMR_OK;
+  });
 }
 
 // the call's odd-extension table (odd_ext.h) in the plan's FskParams for the
@@ -823,21 +790,19 @@ struct EdgeScope {
 
 // d_edge: [B][2 pad] for a raw-integer capture (include/amr.h
 // amr_fsk_demod_host_edges), or null
-int run_fsk(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride, uint8_t* d_out,
-            int64_t out_stride, int64_t* d_len, int64_t* d_sync, const double* d_edge = nullptr) {
-  if (int rc = check_fsk_args(pl, dtype, B, x_stride, out_stride)) return rc;
+int run_fsk(amr_fsk_plan* pl, const DemodIo& io, const double* d_edge = nullptr) {
+  if (int rc = check_demod_args(pl, io, ArgOrder::device)) return rc;
   EdgeScope edge_scope(pl->p, d_edge);
-  for (bool& u : pl->ev_used) u = false;
+  core_clear_used(*pl);
   pl->ran_exact = false;
-  pl->split_now = use_split(pl, B);
+  pl->split_now = use_split(pl, io.B);
   pl->last_split = pl->split_now;
-  if (B == 0) return AMR_OK;
-  if (pl->p.n_bits == 0) return fsk_empty_outputs(pl, B, d_len, d_sync);
-  HIP_TRY(mark_fsk(pl, AMR_TF_LAUNCH, 0));
-  if (int rc = run_fsk_front(pl, d_x, dtype, B, x_stride, false)) return rc;
-  if (int rc = run_fsk_back(pl, B, d_out, out_stride, d_len, d_sync)) return rc;
-  HIP_TRY(mark_fsk(pl, AMR_TF_LAUNCH, 1));
-  return AMR_OK;
+  if (io.B == 0) return AMR_OK;
+  if (pl->p.n_bits == 0) return fsk_empty_outputs(pl, io.B, io.len, io.sync);
+  return timed(*pl, AMR_TF_LAUNCH, [&]() -> int {
+    if (int rc = run_fsk_front(pl, io.x, io.dtype, io.B, io.x_stride, false)) return rc;
+    return run_fsk_back(pl, io);
+  });
 }
 
 // Where the host entries stage the input (max_streams rows of up to 8 B per
@@ -849,11 +814,12 @@ int staging_buffer(amr_fsk_plan* pl, void** buf) {
   *buf = b.get();
   return AMR_OK;
 }
-int stage_input(amr_fsk_plan* pl, const void* x, int dtype, int64_t B, int64_t x_stride, void** staged) {
+int stage_input(amr_fsk_plan* pl, const void* x, int dtype, int64_t B, int64_t x_stride, void** staged,
+                Copy how = Copy::sync) {
   const int64_t es = dtype_size(dtype);
   const int64_t n = pl->p.n;
   if (int rc = staging_buffer(pl, staged)) return rc;
-  return copy_batch_h2d(*staged, x, n * es, x_stride * es, B, pl->stream);
+  return upload_batch(how, *staged, x, n * es, x_stride * es, B, pl->stream);
 }
 
 // the host entries' output staging and the edge table (amr_fsk_demod_host_edges)
@@ -872,7 +838,7 @@ int ensure_out_staging(amr_fsk_plan* pl) {
 // divisions of lc_div, the [L | D] offsets as a bijection onto [0, n)).
 LiveCols plan_live_cols(const FftShape& f, const FskParams& p) {
   LiveCols lc{};
-  static const bool off = [] { const char* e = std::getenv("AMR_FSK_LIVE"); return e && e[0] == '0'; }();
+  static const bool off = !env_not_off("AMR_FSK_LIVE");
   const int64_t q = p.sps / 4, half = p.sps / 2;
   if (off || f.bluestein || f.six || p.n_bits == 0 || q < 1) return lc;
   const int n1 = f.n1, n2 = f.n2;
@@ -903,7 +869,7 @@ LiveCols plan_live_cols(const FftShape& f, const FskParams& p) {
     seen[(size_t)o] = 1;
   }
   lc.on = 1;
-  static const bool no_prune = [] { const char* e = std::getenv("AMR_FFT_PRUNE"); return e && e[0] == '0'; }();
+  static const bool no_prune = !env_not_off("AMR_FFT_PRUNE");
   lc.prune = !no_prune;
   return lc;
 }
@@ -969,7 +935,7 @@ bool fsk_geometry(int64_t n, int64_t sps, int nt, int64_t max_streams, FskGeom& 
                 (2 * m1g * 8 + 8 + 96 * (m1g / kFskSplitConvMinL + 2) + 2 * (strict_row * 8 + 64)) +
             2 * (2 * (n / 4) + 1) * 48 + 2 * (2 * (n / 4) + 1 + 4 * (2 * (n / 4) / 16 + 64) + 64) * 8;
   // the exact path (AMR_FSK_EXACT=0: off), at every length with decisions to make
-  static const bool exact_env = [] { const char* e = std::getenv("AMR_FSK_EXACT"); return !(e && e[0] == '0'); }();
+  static const bool exact_env = env_not_off("AMR_FSK_EXACT");
   g.exact = exact_env && p.n_bits > 0;
   if (g.exact) {
     g.slot_doubles = pf_even(n) + pf_scratch_doubles_n(n);   // the row, then its transforms' scratch
@@ -990,12 +956,8 @@ bool fsk_geometry(int64_t n, int64_t sps, int nt, int64_t max_streams, FskGeom& 
     // (AMR_FSK_KEEPZ=0, an A/B switch: dead tiles in place, the F1 re-run)
     // (AMR_FSK_F1_FMA=1 makes F1 the contracted form, not scipy's order: the
     // exact path must then re-run F1 in scipy's order, so no keep_z)
-    static const bool keepz_env = [] {
-      const char* e = std::getenv("AMR_FSK_KEEPZ");
-      const char* f = std::getenv("AMR_FSK_F1_FMA");
-      return !(e && e[0] == '0') && !(f && f[0] == '1');
-    }();
-    static const bool eager_env = [] { const char* e = std::getenv("AMR_FSK_KEEPZ"); return e && e[0] == '1'; }();
+    static const bool keepz_env = env_not_off("AMR_FSK_KEEPZ") && !env_on("AMR_FSK_F1_FMA");
+    static const bool eager_env = env_on("AMR_FSK_KEEPZ");
     g.keep_z = keepz_env && p.lc.on && (int64_t)p.lc.nd * p.lc.n2 * 2 >= n;
     if (g.keep_z) {
       g.dd = max_streams * (int64_t)p.lc.nd * p.lc.n2 * 16;   // counted: a host entry allocates it
@@ -1022,13 +984,7 @@ constexpr double kFskSplitSafety = 64.0;
 // the split design and F2's FFT bound
 void fsk_tone_gains(const FskIir& f, int nt, IirGains g[2]) {
   for (int t = 0; t < 2; ++t) {
-    Iir fi{};
-    fi.nt = nt;
-    for (int i = 0; i < nt; ++i) {
-      fi.b[i] = f.b[t][i];
-      fi.a[i] = f.a[t][i];
-    }
-    g[t] = iir_gains(fi);
+    g[t] = iir_gains(make_iir(f.b[t], f.a[t], nullptr, nt));
     if (!g[t].ok) return;        // no design and no bound without both
   }
 }
@@ -1125,13 +1081,7 @@ bool fsk_fft_bound(const FskIir& f, const IirGains gains[2], int nt, int64_t n, 
   const double m1 = (double)(n + 2 * (int64_t)pad);
   double zb = 0.0;
   for (int t = 0; t < 2; ++t) {
-    Iir fi{};
-    fi.nt = nt;
-    for (int i = 0; i < nt; ++i) {
-      fi.b[i] = f.b[t][i];
-      fi.a[i] = f.a[t][i];
-    }
-    for (int i = 0; i < nt - 1; ++i) fi.zi[i] = f.zi[t][i];
+    const Iir fi = make_iir(f.b[t], f.a[t], f.zi[t], nt);
     const IirGains& g = gains[t];
     const double R = zi_response_l2(fi);
     if (!(R >= 0.0)) return false;
@@ -1322,7 +1272,7 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
     pl->p.xbits = pl->mem.xbits.as<uint8_t>();
     pl->n_slots = geo.n_slots;
     pl->slot_doubles = geo.slot_doubles;
-    static const bool xstream_on = [] { const char* e = std::getenv("AMR_FSK_XSTREAM"); return e && e[0] == '1'; }();
+    static const bool xstream_on = env_on("AMR_FSK_XSTREAM");
     if (xstream_on) {
       int least = 0, greatest = 0;
       e = hipDeviceGetStreamPriorityRange(&least, &greatest);
@@ -1358,9 +1308,7 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
       const int64_t w = pl->split_w;
       pl->split_tab_host.assign((size_t)(2 * w + 2 * (w + 1)) * 6, 0.0);
       for (int t = 0; t < 2; ++t) {
-        Iir fi{};
-        fi.nt = nt;
-        for (int i = 0; i < nt; ++i) { fi.b[i] = pl->f.b[t][i]; fi.a[i] = pl->f.a[t][i]; fi.zi[i] = pl->f.zi[t][i]; }
+        const Iir fi = make_iir(pl->f.b[t], pl->f.a[t], pl->f.zi[t], nt);
         split_state_tables(fi, w, pl->split_tab_host.data() + (size_t)t * w * 6,
                            pl->split_tab_host.data() + (size_t)(2 * w + t * (w + 1)) * 6);
       }
@@ -1443,10 +1391,7 @@ int amr_fsk_split_strict_design(const double* b, const double* a, const double* 
                                 double* tabs) {
   if (!b || !a || !zi || !consts || nt < 2 || nt > kMaxTaps || w < 1)
     return fail(AMR_E_INVALID, "amr_fsk_split_strict_design: bad argument");
-  Iir f{};
-  f.nt = nt;
-  for (int i = 0; i < nt; ++i) { f.b[i] = b[i]; f.a[i] = a[i]; }
-  for (int i = 0; i < nt - 1; ++i) f.zi[i] = zi[i];
+  const Iir f = make_iir(b, a, zi, nt);
   const int N = nt - 1;
   std::vector<double> tab((size_t)(2 * w + 1) * N);
   split_state_tables(f, w, tab.data(), tab.data() + (size_t)w * N);
@@ -1543,23 +1488,12 @@ int amr_fsk_split_bandpass_host(amr_fsk_plan* plan, const void* x, int dtype, in
 
 int amr_fsk_plan_synchronize(amr_fsk_plan* plan) {
   if (!plan) return fail(AMR_E_INVALID, "plan is NULL");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  HIP_TRY(gate_sync(plan->gate));
-  return AMR_OK;
+  return core_synchronize(*plan);
 }
 
 int amr_fsk_plan_enable_timing(amr_fsk_plan* plan, int on) {
   if (!plan) return fail(AMR_E_INVALID, "plan is NULL");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (on && !plan->ev[0][0]) {
-    for (auto& e : plan->ev)
-      for (auto& h : e) HIP_TRY(hipEventCreate(&h));
-  }
-  plan->timing = on != 0;
-  return AMR_OK;
+  return core_enable_timing(*plan, on);
 }
 
 int amr_fsk_plan_set_exact_mode(amr_fsk_plan* plan, int mode) {
@@ -1587,16 +1521,7 @@ int amr_fsk_plan_exact_streams(amr_fsk_plan* plan, int64_t* count) {
 
 int amr_fsk_plan_timings(amr_fsk_plan* plan, float* ms, int count) {
   if (!plan || !ms) return fail(AMR_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  for (int i = 0; i < count && i < AMR_TF_COUNT; ++i) {
-    ms[i] = -1.0f;
-    if (!plan->timing || !plan->ev_used[i]) continue;
-    HIP_TRY(hipEventSynchronize(plan->ev[i][1]));   // the launch slot may end on a comm stream (a gather)
-    HIP_TRY(hipEventElapsedTime(&ms[i], plan->ev[i][0], plan->ev[i][1]));
-  }
-  return AMR_OK;
+  return core_timings(*plan, ms, count);
 }
 
 int amr_fsk_allgather(amr_comm* comm, const void* d_send, void* d_recv, int64_t bytes_per_rank, amr_fsk_plan* plan) {
@@ -1612,7 +1537,7 @@ int amr_fsk_demod_device(amr_fsk_plan* plan, const void* d_x, int dtype, int64_t
     return fail(AMR_E_INVALID, "amr_fsk_demod_device: NULL argument");
   std::lock_guard<std::mutex> lk(plan->mu);
   HIP_TRY(hipSetDevice(plan->device));
-  return run_fsk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx);
+  return run_fsk(plan, {d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx});
 }
 
 int amr_fsk_demod_device_edges(amr_fsk_plan* plan, const void* d_x, int dtype, int64_t n_streams, int64_t x_stride,
@@ -1622,50 +1547,35 @@ int amr_fsk_demod_device_edges(amr_fsk_plan* plan, const void* d_x, int dtype, i
     return fail(AMR_E_INVALID, "amr_fsk_demod_device_edges: NULL argument");
   std::lock_guard<std::mutex> lk(plan->mu);
   HIP_TRY(hipSetDevice(plan->device));
-  return run_fsk(plan, d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx, d_edges);
+  return run_fsk(plan, {d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}, d_edges);
 }
 
 }  // extern "C"
 
 namespace {
-int fsk_demod_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, const double* edges,
-                   uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
-  if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
-    return fail(AMR_E_INVALID, "amr_fsk_demod_host: NULL argument");
-  if (!dtype_size(dtype)) return fail(AMR_E_INVALID, "unknown dtype");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  if (x_stride < plan->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < plan->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  if (B == 0) return AMR_OK;
-  const int64_t cap = plan->out_cap;
-  if (int rc = ensure_out_staging(plan)) return rc;
-  uint8_t* const d_out = plan->mem.d_out.as<uint8_t>();
-  int64_t *const d_len = plan->mem.d_len.as<int64_t>(), *const d_sync = plan->mem.d_sync.as<int64_t>();
-  for (bool& u : plan->ev_used) u = false;
-  if (plan->p.n_bits == 0) {
-    if (int rc = fsk_empty_outputs(plan, B, d_len, d_sync)) return rc;
-  } else {
+// A host entry (plan_core.h host_round_trip), blocking or queued; edges: the
+// raw-integer capture's table, staged in d_edge
+int fsk_demod_host(amr_fsk_plan* plan, const char* who, const DemodIo& h, Copy how, const double* edges = nullptr) {
+  return host_round_trip(plan, who, h, how, [&]() -> int {
+    amr_fsk_plan::Mem& m = plan->mem;
+    if (int rc = ensure_out_staging(plan)) return rc;
+    DemodIo d{nullptr, h.dtype, h.B, plan->p.n, m.d_out.as<uint8_t>(), plan->out_cap, m.d_len.as<int64_t>(),
+              m.d_sync.as<int64_t>()};
+    core_clear_used(*plan);
+    // no decision window: the empty outputs, and no input staged
+    if (plan->p.n_bits == 0) return fsk_empty_outputs(plan, h.B, d.len, d.sync);
     void* xs = nullptr;
-    if (int rc = stage_input(plan, x, dtype, B, x_stride, &xs)) return rc;
-    const double* d_edge = nullptr;
-    if (edges) {
-      d_edge = plan->mem.d_edge.as<double>();
-      HIP_TRY(hipMemcpyAsync(plan->mem.d_edge.get(), edges, (size_t)(B * 2 * (int64_t)plan->p.pad * 8),
-                             hipMemcpyHostToDevice, plan->stream));
-    }
-    plan->count_sync = true;                 // this call waits anyway: the exact path sized by its own count
-    const int rc = run_fsk(plan, xs, dtype, B, plan->p.n, d_out, cap, d_len, d_sync, d_edge);
+    if (int rc = stage_input(plan, h.x, h.dtype, h.B, h.x_stride, &xs, how)) return rc;
+    d.x = xs;
+    if (edges)
+      HIP_TRY(hipMemcpyAsync(m.d_edge.get(), edges, (size_t)(h.B * 2 * (int64_t)plan->p.pad * 8), hipMemcpyHostToDevice,
+                             plan->stream));
+    // a blocking call waits anyway: the exact path sized by the batch's own count
+    plan->count_sync = how == Copy::sync;
+    const int rc = run_fsk(plan, d, edges ? m.d_edge.as<double>() : nullptr);
     plan->count_sync = false;
-    if (rc) return rc;
-  }
-  if (int rc = copy_batch_d2h(out, out_stride, d_out, cap, out_stride < cap ? out_stride : cap, B, plan->stream))
     return rc;
-  HIP_TRY(hipMemcpyAsync(out_len, d_len, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipMemcpyAsync(sync_idx, d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, plan->stream));
-  HIP_TRY(hipStreamSynchronize(plan->stream));
-  return AMR_OK;
+  });
 }
 }  // namespace
 
@@ -1673,57 +1583,24 @@ extern "C" {
 
 int amr_fsk_demod_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, uint8_t* out,
                        int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
-  return fsk_demod_host(plan, x, dtype, B, x_stride, nullptr, out, out_stride, out_len, sync_idx);
+  return fsk_demod_host(plan, "amr_fsk_demod_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                        Copy::sync);
 }
 
 int amr_fsk_demod_host_edges(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
                              const double* edges, uint8_t* out, int64_t out_stride, int64_t* out_len,
                              int64_t* sync_idx) {
   if (B && !edges) return fail(AMR_E_INVALID, "amr_fsk_demod_host_edges: NULL edges");
-  return fsk_demod_host(plan, x, dtype, B, x_stride, edges, out, out_stride, out_len, sync_idx);
+  return fsk_demod_host(plan, "amr_fsk_demod_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                        Copy::sync, edges);
 }
 
 // Queued host entry (as amr_psk_demod_host_async): upload, demod, download on
 // the plan's stream, no wait; host buffers untouched until amr_fsk_plan_synchronize.
 int amr_fsk_demod_host_async(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
                              uint8_t* out, int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
-  if (!plan || (B && (!x || !out || !out_len || !sync_idx)))
-    return fail(AMR_E_INVALID, "amr_fsk_demod_host_async: NULL argument");
-  const int64_t es = dtype_size(dtype);
-  if (!es) return fail(AMR_E_INVALID, "unknown dtype");
-  std::lock_guard<std::mutex> lk(plan->mu);
-  HIP_TRY(hipSetDevice(plan->device));
-  if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
-  if (x_stride < plan->p.n) return fail(AMR_E_INVALID, "x_stride < n_samples");
-  if (out_stride < plan->out_cap - 1 || out_stride < 1) return fail(AMR_E_INVALID, "out_stride too small");
-  if (B == 0) return AMR_OK;
-  const int64_t n = plan->p.n;
-  const int64_t cap = plan->out_cap;
-  if (int rc = ensure_out_staging(plan)) return rc;
-  uint8_t* const d_out = plan->mem.d_out.as<uint8_t>();
-  int64_t *const d_len = plan->mem.d_len.as<int64_t>(), *const d_sync = plan->mem.d_sync.as<int64_t>();
-  hipStream_t st = plan->stream;
-  for (bool& u : plan->ev_used) u = false;
-  if (plan->p.n_bits == 0) {
-    if (int rc = fsk_empty_outputs(plan, B, d_len, d_sync)) return rc;
-  } else {
-    void* xs = nullptr;
-    if (int rc = staging_buffer(plan, &xs)) return rc;
-    if (x_stride == n)
-      HIP_TRY(hipMemcpyAsync(xs, x, (size_t)(B * n * es), hipMemcpyHostToDevice, st));
-    else
-      HIP_TRY(hipMemcpy2DAsync(xs, (size_t)(n * es), x, (size_t)(x_stride * es), (size_t)(n * es), (size_t)B,
-                               hipMemcpyHostToDevice, st));
-    if (int rc = run_fsk(plan, xs, dtype, B, n, d_out, cap, d_len, d_sync)) return rc;
-  }
-  if (out_stride == cap)
-    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)(B * cap), hipMemcpyDeviceToHost, st));
-  else
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, d_out, (size_t)cap, (size_t)std::min(out_stride, cap),
-                             (size_t)B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_len, d_len, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sync_idx, d_sync, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  return AMR_OK;
+  return fsk_demod_host(plan, "amr_fsk_demod_host_async",
+                        {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx}, Copy::async);
 }
 
 int amr_fsk_envelopes_host(amr_fsk_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,

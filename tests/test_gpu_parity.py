@@ -267,11 +267,11 @@ def test_decode_wav_file_end_to_end(golden, tmp_path, monkeypatch):
         assert got == case["files"], case["id"]
 
 
-@pytest.mark.parametrize("layout", ["row", "split"])
+@pytest.mark.parametrize("layout", ["row", "lane", "split"])
 def test_timing_hooks(layout):
     """Per-stage HIP-event times of a call; the time-split layout times its
     two low-pass passes in the lowpass_fwd slot and its gated serial fallback
-    in lowpass_exact."""
+    in lowpass_exact; the lane layout's one low-pass kernel is lowpass_fwd."""
     import _amr
     import synth
     x = synth.qpsk_batch(64, 20000, 9600, seed=1, distinct=2)
@@ -281,9 +281,8 @@ def test_timing_hooks(layout):
     plan.demod_host(x)
     assert plan.last_layout() == layout
     t = plan.timings()
-    want = {"bandpass", "lowpass_fwd", "lowpass_bwd", "sync_pack"} if layout == "row" else \
-        {"bandpass", "lowpass_fwd", "lowpass_exact", "sync_pack"}
-    assert set(t) >= want
+    want = {"bandpass", "lowpass_fwd", "lowpass_exact", "sync_pack", "launch"}
+    assert set(t) == (want | {"lowpass_bwd"} if layout == "row" else want)
     assert all(v > 0 for v in t.values())
 
 
