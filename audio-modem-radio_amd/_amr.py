@@ -43,7 +43,7 @@ EXPORTS = [
     "amr_psk_plan_bytes_estimate", "amr_fsk_plan_bytes_estimate",
     "amr_psk_plan_synchronize", "amr_psk_plan_enable_timing", "amr_psk_plan_timings", "amr_psk_plan_set_inflight",
     "amr_psk_plan_exact_streams", "amr_psk_demod_host", "amr_psk_demod_device", "amr_psk_demod_fec_device",
-    "amr_psk_slice_host", "amr_psk_plan_last_layout", "amr_synth_tile_noise",
+    "amr_psk_slice_host", "amr_sync_pack_host", "amr_psk_plan_last_layout", "amr_synth_tile_noise",
     "amr_psk_demod_host_async", "amr_fsk_demod_host_async", "amr_host_register", "amr_host_unregister",
     "amr_host_alloc", "amr_host_free",
     "amr_fsk_plan_create", "amr_fsk_plan_destroy", "amr_fsk_plan_out_capacity", "amr_fsk_plan_scratch_bytes",
@@ -204,6 +204,41 @@ def psk_slice(kind: str, sym: np.ndarray) -> np.ndarray:
     return bits[:, :nbits]
 
 
+def sync_pack(bits, n_words=None, out_stride=None, fill=0xA5, n_bits=None):
+    """The sync search and byte pack alone on the GPU (k_sync_pack through
+    amr_sync_pack_host): bits [B][n_bits] of 0/1 -> (out [B][out_stride] uint8,
+    out_len [B], sync_idx [B]).  out is pre-filled with `fill` and returned
+    whole, so a caller can look past out_len.  n_words (default ceil(n_bits/32),
+    at least 1) and out_stride (default n_bits // 8) size the two buffers.
+    With n_bits given, `bits` may be wider, up to n_words * 32 columns: the
+    columns past n_bits are stale data the kernel must not read."""
+    require_gpu()
+    bits = np.ascontiguousarray(np.atleast_2d(bits), np.uint8)
+    B = bits.shape[0]
+    n_bits = bits.shape[1] if n_bits is None else int(n_bits)
+    nw = max(1, (n_bits + 31) // 32) if n_words is None else int(n_words)
+    stride = n_bits // 8 if out_stride is None else int(out_stride)
+    if not n_bits <= bits.shape[1] <= max(nw * 32, n_bits):
+        raise ValueError("sync_pack: bits holds n_bits to n_words * 32 columns")
+    words = pack_words(bits, nw)
+    out = np.full((B, max(stride, 0)), fill, np.uint8)
+    ln = np.zeros(B, np.int64)
+    sync = np.zeros(B, np.int64)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_sync_pack_host(ptr(words), B, nw, n_bits, ptr(out), stride, ptr(ln), ptr(sync)))
+    return out, ln, sync
+
+
+def pack_words(bits: np.ndarray, n_words: int) -> np.ndarray:
+    """bits [B][n] of 0/1 as [B][n_words] uint32, MSB first, zero past n (host
+    only; psk_slice's unpacking the other way round).  A row too long for
+    n_words is cut, so that the library sees, and refuses, the short n_words."""
+    B, n = bits.shape
+    full = np.zeros((B, n_words * 32), np.uint8)
+    full[:, :min(n, n_words * 32)] = bits[:, :n_words * 32]
+    return np.packbits(full, axis=1).reshape(B, n_words, 4).view(">u4").astype(np.uint32).reshape(B, n_words)
+
+
 def frame_parse(raws, max_cands: int = 64):
     """Batched decoder.parse_fbp_stream_enhanced scan (decoder.py:142-208) on
     the GPU: for each bytes object, (n_candidates, records[:min(n, max_cands)])
@@ -306,6 +341,7 @@ def lib():
             "amr_psk_split_strict_design": (I32, [P, P, P, I32, P, P, P, I32, I64, I64, I64, P, P]),
             "amr_psk_demod_fec_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, P]),
             "amr_psk_slice_host": (I32, [I32, P, I64, I64, P]),
+            "amr_sync_pack_host": (I32, [P, I64, I64, I64, P, I64, P, P]),
             "amr_psk_plan_last_layout": (I32, [P]),
             "amr_psk_plan_set_layout": (I32, [P, I32]),
             "amr_psk_plan_split_info": (I32, [P, P, P, P, P, P]),

@@ -1520,6 +1520,38 @@ int amr_psk_soft_host(int kind, const double* sym, int64_t n_streams, int64_t n_
   return psk_symbol_stages("amr_psk_soft_host", kind, sym, n_streams, n_sym, nullptr, soft);
 }
 
+// ---- the sync search and byte pack alone (modem.py:243-266), for its length and offset tests ----
+int amr_sync_pack_host(const uint32_t* words, int64_t n_streams, int64_t n_words, int64_t n_bits, uint8_t* out,
+                       int64_t out_stride, int64_t* out_len, int64_t* sync_idx) {
+  if (n_streams < 0 || n_words < 0 || n_bits < 0 || out_stride < 0 || n_streams > 0x7fffffff)
+    return fail(AMR_E_INVALID, "amr_sync_pack_host: negative count");
+  if (n_words < (n_bits + 31) / 32) return fail(AMR_E_INVALID, "amr_sync_pack_host: n_words < ceil(n_bits / 32)");
+  if (out_stride < n_bits / 8) return fail(AMR_E_INVALID, "amr_sync_pack_host: out_stride < n_bits / 8");
+  if (n_streams && (!out_len || !sync_idx || (n_words && !words) || (out_stride && !out)))
+    return fail(AMR_E_INVALID, "amr_sync_pack_host: NULL argument");
+  if (n_streams == 0) return AMR_OK;
+  const auto bad = [](hipError_t e) {
+    return fail(AMR_E_HIP, std::string("amr_sync_pack_host: ") + hipGetErrorString(e));
+  };
+  const int64_t wbytes = n_streams * n_words * 4, obytes = n_streams * out_stride;
+  DevBuf d_words, d_out, d_len, d_sync;
+  HIP_TRY_ELSE(d_words.reserve(wbytes > 0 ? wbytes : 4, nullptr), bad);
+  HIP_TRY_ELSE(d_out.reserve(obytes > 0 ? obytes : 1, nullptr), bad);
+  HIP_TRY_ELSE(d_len.reserve(n_streams * 8, nullptr), bad);
+  HIP_TRY_ELSE(d_sync.reserve(n_streams * 8, nullptr), bad);
+  if (wbytes > 0) HIP_TRY_ELSE(hipMemcpy(d_words.get(), words, (size_t)wbytes, hipMemcpyHostToDevice), bad);
+  // `out` goes in as the caller filled it, so every byte the kernel leaves alone comes back unchanged
+  if (obytes > 0) HIP_TRY_ELSE(hipMemcpy(d_out.get(), out, (size_t)obytes, hipMemcpyHostToDevice), bad);
+  HIP_TRY_ELSE(launch_sync_pack(d_words.as<uint32_t>(), n_words, n_bits, n_streams, d_out.as<uint8_t>(), out_stride,
+                                d_len.as<int64_t>(), d_sync.as<int64_t>(), nullptr),
+               bad);
+  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
+  if (obytes > 0) HIP_TRY_ELSE(hipMemcpy(out, d_out.get(), (size_t)obytes, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(out_len, d_len.get(), (size_t)n_streams * 8, hipMemcpyDeviceToHost), bad);
+  HIP_TRY_ELSE(hipMemcpy(sync_idx, d_sync.get(), (size_t)n_streams * 8, hipMemcpyDeviceToHost), bad);
+  return AMR_OK;
+}
+
 // ---- FBP frame parse (decoder.py:142-208) ------------------------------------
 int amr_frame_parse_device(amr_psk_plan* plan, const uint8_t* d_in, int64_t in_stride, const int64_t* d_in_len,
                            int64_t n, int64_t max_cands, int32_t* d_n_cands, amr_frame_rec* d_recs) {

@@ -86,7 +86,7 @@ extern "C" {
                                   _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL; the
                                   convolutional code (amr_conv_encoded_len, amr_conv_encode_host,
                                   amr_viterbi_work_bytes, amr_viterbi_decode_host / _device);
-                                  amr_psk_plan_last_lowpass (AMR_LP_*) */
+                                  amr_psk_plan_last_lowpass (AMR_LP_*); amr_sync_pack_host (diagnostic) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -344,6 +344,21 @@ int amr_psk_demod_fec_device(amr_psk_plan *plan, const void *d_x, int dtype, int
  * For testing the decision at sector edges directly. */
 int amr_psk_slice_host(int kind, const double *sym, int64_t n_streams, int64_t n_sym, uint32_t *words);
 
+/* The stage after the slicer alone: the first "0100011001000010" in each
+ * stream's n_bits decided bits (bit_str.find, modem.py:247-248) and the whole
+ * bytes from there, or from bit 0 without one (modem.py:250-264), MSB first.
+ * words [n_streams][n_words], bits MSB first, n_words >= ceil(n_bits/32); bits
+ * past n_bits and words past ceil(n_bits/32) are never looked at.  out
+ * [n_streams][out_stride], out_stride >= n_bits/8: out_len[s] bytes of row s
+ * are written and every other byte of out is returned as it was passed in.
+ * sync_idx[s] is the bit index of the sync, -1 without one.  AMR_E_INVALID for
+ * a null pointer, a negative count or one of the two sizes too small, before
+ * any device work.  Synchronous, current device.  A diagnostic entry like
+ * amr_psk_slice_host: for testing the search and the packer at every length
+ * and offset directly. */
+int amr_sync_pack_host(const uint32_t *words, int64_t n_streams, int64_t n_words, int64_t n_bits, uint8_t *out,
+                       int64_t out_stride, int64_t *out_len, int64_t *sync_idx);
+
 /* ---- FSK demodulation (modem.py:298-341) ------------------------------------
  * Replaces modem.fsk_demodulate(samples, baud, mark, space, fs) for a batch of
  * equal-length streams (also fsk_high_speed_demodulate modem.py:355-356,
@@ -521,7 +536,9 @@ int amr_fec_decode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_
  * pass them.  n_cands[s] = occurrences found (may exceed max_cands: records
  * are kept for the first min(n_cands, max_cands, 256); a caller seeing more
  * parses that stream itself).  recs: [n][max_cands], 1 <= max_cands <=
- * AMR_FRAME_MAX_CANDS (larger is AMR_E_INVALID).  The host turns records
+ * AMR_FRAME_MAX_CANDS (larger is AMR_E_INVALID).  A header field that the
+ * checks never reached (the ones read after the check that stopped the
+ * candidate) is 0; calc_crc is set for OK / CRC_BAD.  The host turns records
  * into the reference's list of {'name', 'data', 'final_crc'} and log lines. */
 #define AMR_FRAME_MAX_CANDS 256     /* records kept per stream (LDS list of k_frame_parse) */
 #define AMR_FRAME_SHORT 0          /* start + 30 > len(raw)            decoder.py:165 */

@@ -129,6 +129,40 @@ def test_frame_parse_argument_checks(built_lib):
         _amr.frame_parse([b"FBPC"])                                                         # no GPU here
 
 
+def test_sync_pack_argument_checks(built_lib):
+    """amr_sync_pack_host refuses bad arguments before any device work: a null
+    pointer, a negative count, n_words < ceil(n_bits/32), out_stride < n_bits/8."""
+    import _amr
+    L = _amr.lib()
+    words = np.zeros((2, 3), np.uint32)
+    out = np.zeros((2, 12), np.uint8)
+    ln = np.zeros(2, np.int64)
+    sy = np.zeros(2, np.int64)
+    w, o, l, s = (_amr.ptr(v) for v in (words, out, ln, sy))
+    bad = _amr.AMR_E_INVALID
+    assert L.amr_sync_pack_host(None, 2, 3, 96, o, 12, l, s) == bad
+    assert b"NULL" in L.amr_last_error()
+    assert L.amr_sync_pack_host(w, 2, 3, 96, None, 12, l, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, 96, o, 12, None, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, 96, o, 12, l, None) == bad
+    assert L.amr_sync_pack_host(w, -1, 3, 96, o, 12, l, s) == bad
+    assert b"negative" in L.amr_last_error()
+    assert L.amr_sync_pack_host(w, 2, -3, 96, o, 12, l, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, -96, o, 12, l, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, 96, o, -12, l, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, 97, o, 12, l, s) == bad               # 97 bits need 4 words
+    assert b"n_words" in L.amr_last_error()
+    assert L.amr_sync_pack_host(w, 2, 2, 65, o, 8, l, s) == bad
+    assert L.amr_sync_pack_host(w, 2, 3, 96, o, 11, l, s) == bad               # 96 bits pack to 12 bytes
+    assert b"out_stride" in L.amr_last_error()
+    assert L.amr_sync_pack_host(None, 0, 0, 0, None, 0, None, None) == _amr.AMR_OK   # empty batch
+    if _amr.device_count() < 1:
+        with pytest.raises(_amr.AmrError):
+            _amr.sync_pack(np.zeros((1, 32), np.uint8))                        # no GPU here
+    words = _amr.pack_words(np.array([[0, 1] * 20], np.uint8), 2)
+    assert words.tolist() == [[0x55555555, 0x55000000]]
+
+
 def test_set_inflight_argument_checks(built_lib):
     import _amr
     L = _amr.lib()
