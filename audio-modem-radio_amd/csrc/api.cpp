@@ -528,6 +528,10 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
   PskParams& p = pl->p;
   bool zodd = true;
   for (int i = 1; i < bp_nt; i += 2) zodd = zodd && is_pos_zero(bp_b[i]);
+  // the shortened steps multiply y by a[1], a[3], ...: with |y| >= 2^-1015 (the
+  // kernels' detector, psk_common.h) a tap of at least 2^-40 keeps the product
+  // from underflowing to a zero; butter(4, band) has them near 1
+  for (int i = 1; i < bp_nt; i += 2) zodd = zodd && std::isfinite(bp_a[i]) && std::fabs(bp_a[i]) >= 0x1p-40;
   p.bp_zero_odd = zodd ? 1 : 0;
   // butter()'s numerators are k * poly(zeros at +-1): palindromic, and the
   // kernels then form each distinct product x * b[i] once (psk_lane_kernels.hip)

@@ -127,17 +127,35 @@ __device__ __forceinline__ double df2t_step(double (&z)[NS], const Iir& f, doubl
 }
 
 // The band-pass's odd taps b1, b3, b5, b7 are exactly +0.0 (butter(4, band);
-// the plan checks, PskParams::bp_zero_odd).  The step without them --
-// z[i] = z[i+1] - y*a[i+1] for even i -- is scipy's bit for bit whenever
-// z[i+1] + x*(+0.0) == z[i+1], i.e. unless z[i+1] is -0.0 (or x is inf / NaN,
-// which makes the final states non-finite).  The detector keeps the minimum
-// |hi word| (as float) of z1, z3, z5, z7 before every step: >= FLT_MIN means
-// |z| >= 2^-1015, never a zero; a stream that fails, or ends non-finite, is
-// flagged and its group re-run with every tap (k_bp_lane2's FIXUP form).
-// 26 instead of 34 FP64 per step, + 2 v_min3_f32.
+// the plan checks, PskParams::bp_zero_odd).  The step without them (bp_step_zo
+// below) computes z[i] = z[i+1] - y*a[i+1] for even i where scipy computes
+// (z[i+1] + x*(+0.0)) - y*a[i+1].  When are the two the same bits?
+//   * x finite: x*(+0.0) is a zero, and z[i+1] + (a zero) is z[i+1] itself
+//     unless z[i+1] is -0.0 and the product +0.0: the sum is then +0.0.
+//   * (+0.0) - p and (-0.0) - p are the same bits for every p but p == +0.0:
+//     -p for p non-zero (NaN included), +0.0 for p == -0.0.
+//   * So the forms can differ only in a step whose p = y*a[i+1] is a zero: y
+//     is a zero, or the product underflows to one.
+//   * x inf or NaN: x*(+0.0) is NaN and scipy's states are NaN from there on;
+//     the shortened step's y = z0 + b0*x is not finite either, then z0 =
+//     z1 - y*a1 is not, then the next y: the final z0 is not finite.
+// Hence the detector (zo_watch_y): the minimum |hi word| (as float) of every
+// step's y; >= FLT_MIN means |y| >= 2^-1015, and the plan admits the shortened
+// step only for |a1|, |a3|, |a5|, |a7| >= 2^-40 (bp_zero_odd), so |p| >=
+// 2^-1055: never a zero.  A stream that fails, or ends with a non-finite
+// state, is flagged and its group re-run with every tap (k_bp_lane2's FIXUP
+// form); digital silence drives y to zero and is flagged.  One v_min3_f32 per
+// two steps (the kernels take steps in pairs; a single step passes y twice).
+// 26 instead of 34 FP64 per step.
 // The numerator is also palindromic (b8 == b0, b6 == b2 bit for bit,
 // PskParams::bp_sym), so x*b8 IS x*b0 and x*b6 IS x*b2: 3 products, not 5.
 // 23 FP64 per step instead of 34.
+__device__ __forceinline__ void zo_watch_y(float& acc, double y0, double y1) { acc = tiny_min3(acc, y0, y1); }
+
+// The earlier, stricter detector (AMR_BP_ZDET=0, kept for A/B runs and the
+// parity test): the minimum |hi word| of z1, z3, z5, z7 before every step,
+// >= FLT_MIN meaning that no sum z[i+1] + x*(+0.0) met a -0.0 at all.
+// 2 v_min3_f32 per step.
 __device__ __forceinline__ double df2t_step_zo(double (&z)[8], const Iir& f, double x, float& acc) {
   acc = tiny_min3(acc, z[1], z[3]);
   acc = tiny_min3(acc, z[5], z[7]);

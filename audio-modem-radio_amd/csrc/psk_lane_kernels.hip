@@ -48,6 +48,7 @@
 
 #include "amr.h"
 #include "amr_internal.h"
+#include "env_switch.h"
 #include "psk_common.h"
 
 namespace amr {
@@ -58,13 +59,23 @@ constexpr int kLpT2 = 20;    // the same for the role-split low-pass (LDS: 2 com
 
 // (the DF-II-T step functions df2t_step / df2t_step_zo / lp_step: psk_common.h)
 
-template <bool ZO>
+// ZO: 0 every tap; kZoY the zero odd taps skipped, the detector on y
+// (bp_watch, one v_min3_f32 per pair of steps); kZoZ the same steps under the
+// earlier four-state detector inside the step (AMR_BP_ZDET=0)
+constexpr int kZoY = 1, kZoZ = 2;
+template <int ZO>
 __device__ __forceinline__ double bp_step(double (&z)[8], const Iir& f, double x, float& acc) {
-  if constexpr (ZO) return df2t_step_zo(z, f, x, acc);
+  if constexpr (ZO == kZoZ) return df2t_step_zo(z, f, x, acc);
+  else if constexpr (ZO == kZoY) return bp_step_zo(z, f, x);
   else return df2t_step<8>(z, f, x);
 }
+// the outputs of the two steps just taken (of a single step: y twice)
+template <int ZO>
+__device__ __forceinline__ void bp_watch(float& acc, double y0, double y1) {
+  if constexpr (ZO == kZoY) zo_watch_y(acc, y0, y1);
+}
 
-template <bool ZO>
+template <int ZO>
 __device__ __forceinline__ bool bp_bad(float acc, const double (&z)[8]) {
   if constexpr (!ZO) return false;
   bool bad = !(acc >= kTinyHi);
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(64 * WPB) void k_bp_lane(PskBuffers buf, PskParams 
 // (checkpoint at the start of every tile, no output) + tail (edge outputs);
 // the zero-tap detector flags a stream it cannot vouch for.  Used by
 // k_bp_lane2's forward role and, on its own, by k_bp_fwd.
-template <typename T, bool ZO>
+template <typename T, int ZO>
 __device__ __forceinline__ void bp_forward_pass(const PskBuffers& buf, const PskParams& p, const Iir& f, int64_t w,
                                                 int lane) {
   constexpr int TB = kBpT;
@@ -232,7 +243,10 @@ __device__ __forceinline__ void bp_forward_pass(const PskBuffers& buf, const Psk
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = f.zi[j] * e0;
   }
-  for (int jj = 0; jj < pad; ++jj) (void)bp_step<ZO>(z, f, ox.left(jj), acc);
+  for (int jj = 0; jj < pad; ++jj) {
+    const double y = bp_step<ZO>(z, f, ox.left(jj), acc);
+    bp_watch<ZO>(acc, y, y);
+  }
   v4u xr[NL];
   if (nt > 0) load_tile(0, xr);
   for (int64_t t = 0; t < nt; ++t) {
@@ -243,11 +257,23 @@ __device__ __forceinline__ void bp_forward_pass(const PskBuffers& buf, const Psk
     for (int k = 0; k < NL; ++k) cur[k] = xr[k];
     load_tile(t + 1 < nt ? t + 1 : t, xr);
 #pragma unroll
-    for (int k = 0; k < TB; ++k) (void)bp_step<ZO>(z, f, tile_x(cur, k), acc);
+    for (int k = 0; k < TB; k += 2) {
+      const double y0 = bp_step<ZO>(z, f, tile_x(cur, k), acc);
+      const double y1 = bp_step<ZO>(z, f, tile_x(cur, k + 1), acc);
+      bp_watch<ZO>(acc, y0, y1);
+    }
   }
   int e = 0;
-  for (int64_t i = i_tail; i < n; ++i) eb[(e++) * 64] = bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc);
-  for (int jj = 0; jj < pad; ++jj) eb[(e++) * 64] = bp_step<ZO>(z, f, ox.right(jj), acc);
+  for (int64_t i = i_tail; i < n; ++i) {
+    const double y = bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc);
+    bp_watch<ZO>(acc, y, y);
+    eb[(e++) * 64] = y;
+  }
+  for (int jj = 0; jj < pad; ++jj) {
+    const double y = bp_step<ZO>(z, f, ox.right(jj), acc);
+    bp_watch<ZO>(acc, y, y);
+    eb[(e++) * 64] = y;
+  }
   if (bp_bad<ZO>(acc, z) && s <= last) atomicOr(&buf.bp_flags[s], 1);
 }
 
@@ -255,7 +281,7 @@ __device__ __forceinline__ void bp_forward_pass(const PskBuffers& buf, const Psk
 // PRE> then runs only the re-run / backward roles.  The forward pass no
 // longer holds an idle backward wave and its LDS for half the band-pass's
 // life.
-template <typename T, bool ZO>
+template <typename T, int ZO>
 __global__ __launch_bounds__(256) void k_bp_fwd(PskBuffers buf, PskParams p, Iir f) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -288,7 +314,7 @@ __global__ __launch_bounds__(256) void k_bp_fwd(PskBuffers buf, PskParams p, Iir
 // NT: which access classes go non-temporal (psk_common.h: kNtFStore the f
 // stores, kNtCk the checkpoints and edge rows, kNtX the x tiles); 0 for the
 // PRE, CK = 2 and F32F variants.
-template <typename T, int GPB, bool ZO, bool FIXUP = false, bool PRE = false, int CK = 1, bool F32F = false, int NT = 0>
+template <typename T, int GPB, int ZO, bool FIXUP = false, bool PRE = false, int CK = 1, bool F32F = false, int NT = 0>
 __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
   static_assert(NT == 0 || (!PRE && CK == 1 && !F32F), "cache policies: the default paths only");
   constexpr bool NTF = (NT & kNtFStore) != 0, NTC = (NT & kNtCk) != 0, NTX = (NT & kNtX) != 0;
@@ -350,7 +376,10 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = f.zi[j] * e0;
     }
-    for (int jj = 0; jj < pad; ++jj) (void)bp_step<ZO>(z, f, ox.left(jj), acc);
+    for (int jj = 0; jj < pad; ++jj) {
+      const double y = bp_step<ZO>(z, f, ox.left(jj), acc);
+      bp_watch<ZO>(acc, y, y);
+    }
     v4u xr[NL];
     if (nt > 0) load_tile(0, xr);
     for (int64_t t = 0; t < nt; ++t) {
@@ -363,11 +392,23 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
       for (int k = 0; k < NL; ++k) cur[k] = xr[k];
       load_tile(t + 1 < nt ? t + 1 : t, xr);
 #pragma unroll
-      for (int k = 0; k < TB; ++k) (void)bp_step<ZO>(z, f, tile_x(cur, k), acc);
+      for (int k = 0; k < TB; k += 2) {
+        const double y0 = bp_step<ZO>(z, f, tile_x(cur, k), acc);
+        const double y1 = bp_step<ZO>(z, f, tile_x(cur, k + 1), acc);
+        bp_watch<ZO>(acc, y0, y1);
+      }
     }
     int e = 0;
-    for (int64_t i = i_tail; i < n; ++i) st_pol<NTC>(&eb[(e++) * 64], bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc));
-    for (int jj = 0; jj < pad; ++jj) st_pol<NTC>(&eb[(e++) * 64], bp_step<ZO>(z, f, ox.right(jj), acc));
+    for (int64_t i = i_tail; i < n; ++i) {
+      const double y = bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc);
+      bp_watch<ZO>(acc, y, y);
+      st_pol<NTC>(&eb[(e++) * 64], y);
+    }
+    for (int jj = 0; jj < pad; ++jj) {
+      const double y = bp_step<ZO>(z, f, ox.right(jj), acc);
+      bp_watch<ZO>(acc, y, y);
+      st_pol<NTC>(&eb[(e++) * 64], y);
+    }
     if (bp_bad<ZO>(acc, z) && s <= last) atomicOr(&buf.bp_flags[s], 1);
     // the checkpoints are re-read by this wave (its re-run role below), the
     // edge rows by the backward wave of the same workgroup behind the barrier
@@ -482,6 +523,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
       for (int j = 0; j < 8; ++j) zb[j] = f.zi[j] * ylast;
       for (int e = ne - 1; e >= 0; --e) {
         const double y = bp_step<ZO>(zb, f, ld_pol<NTC>(&eb[e * 64]), acc);
+        bp_watch<ZO>(acc, y, y);
         const int64_t i = i_tail + e;
         if (i < n) {
           if constexpr (F32F) {
@@ -505,6 +547,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
           const double2 yy = ybuf[k][lane];
           const double y1 = bp_step<ZO>(zb, f, yy.y, acc);
           const double y0 = bp_step<ZO>(zb, f, yy.x, acc);
+          bp_watch<ZO>(acc, y1, y0);
           if constexpr (F32F) {
             *reinterpret_cast<float2*>(fp32 + k * 64) = make_float2((float)y0, (float)y1);
             pk_acc(y0);
@@ -1452,9 +1495,19 @@ static int bp_ck() {
 
 static int bp_zero_taps(const PskParams& p) {
   // skip the band-pass's +0.0 odd taps (detector + exact re-run of flagged
-  // groups): AMR_BP_ZO=0 computes every tap instead
-  static const int v = [] { const char* e = getenv("AMR_BP_ZO"); return e && e[0] == '0' ? 0 : 1; }();
-  return v && p.bp_zero_odd && p.bp_sym;
+  // groups): AMR_BP_ZO=0 computes every tap instead.  Which detector vouches
+  // for the shortened steps (psk_common.h): the one on y (kZoY), or with
+  // AMR_BP_ZDET=0 the earlier watch of four states (kZoZ)
+  static const bool on = env_not_off("AMR_BP_ZO");
+  static const int det = env_not_off("AMR_BP_ZDET") ? kZoY : kZoZ;
+  return on && p.bp_zero_odd && p.bp_sym ? det : 0;
+}
+// fn(std::integral_constant<int, ZO>) for the band-pass step in force
+template <typename Fn>
+static void with_bp_zo(int zo, Fn&& fn) {
+  if (zo == kZoY) fn(std::integral_constant<int, kZoY>{});
+  else if (zo == kZoZ) fn(std::integral_constant<int, kZoZ>{});
+  else fn(std::integral_constant<int, 0>{});
 }
 
 template <typename T>
@@ -1469,12 +1522,14 @@ static hipError_t launch_bp(const PskBuffers& b, const PskParams& p, const Iir& 
     hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((g + 1) / 2)), block(256);
-    if (bp_zero_taps(p)) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
-    else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
+    with_bp_zo(bp_zero_taps(p), [&](auto z) {
+      hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 1, true>), grid, block, 0, st, b, p, f,
+                         lane_dev_fence());
+    });
     return hipGetLastError();
   }
   if (bp_split()) {
-    const bool zo = bp_zero_taps(p);
+    const int zo = bp_zero_taps(p);
     if (zo) {
       hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
       if (e != hipSuccess) return e;
@@ -1482,37 +1537,36 @@ static hipError_t launch_bp(const PskBuffers& b, const PskParams& p, const Iir& 
     const dim3 grid((unsigned)(lane_wpb() >= 2 ? (g + 1) / 2 : g)), block(lane_wpb() >= 2 ? 256 : 128);
     if (lane_wpb() >= 2 && bp_prefwd()) {
       const dim3 fgrid((unsigned)((g + 3) / 4));
-      if (zo) {
-        hipLaunchKernelGGL((k_bp_fwd<T, true>), fgrid, dim3(256), 0, st, b, p, f);
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      } else {
-        hipLaunchKernelGGL((k_bp_fwd<T, false>), fgrid, dim3(256), 0, st, b, p, f);
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      }
+      with_bp_zo(zo, [&](auto z) {
+        constexpr int ZO = decltype(z)::value;
+        hipLaunchKernelGGL((k_bp_fwd<T, ZO>), fgrid, dim3(256), 0, st, b, p, f);
+        hipLaunchKernelGGL((k_bp_lane2<T, 2, ZO, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      });
     } else if (lane_wpb() >= 2 && bp_ck() == 2) {
-      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 2>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      else hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 2>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      with_bp_zo(zo, [&](auto z) {
+        hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 2>), grid, block, 0, st, b, p, f,
+                           lane_dev_fence());
+      });
     } else if (lane_wpb() >= 2) {
       // the default path: the cache policies of AMR_LANE_NT (its fix-up launch below inherits them)
       const bool ok = with_lane_nt([&](auto m) {
         constexpr int NT = decltype(m)::value;
-        if (zo)
-          hipLaunchKernelGGL((k_bp_lane2<T, 2, true, false, false, 1, false, NT>), grid, block, 0, st, b, p, f,
-                             lane_dev_fence());
-        else
-          hipLaunchKernelGGL((k_bp_lane2<T, 2, false, false, false, 1, false, NT>), grid, block, 0, st, b, p, f,
-                             lane_dev_fence());
+        with_bp_zo(zo, [&](auto z) {
+          hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 1, false, NT>), grid, block, 0, st, b, p,
+                             f, lane_dev_fence());
+        });
         if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
-          hipLaunchKernelGGL((k_bp_lane2<T, 1, false, true, false, 1, false, NT>), dim3((unsigned)g), dim3(128), 0, st, b,
+          hipLaunchKernelGGL((k_bp_lane2<T, 1, 0, true, false, 1, false, NT>), dim3((unsigned)g), dim3(128), 0, st, b,
                              p, f, lane_dev_fence());
       });
       return ok ? hipGetLastError() : hipErrorInvalidValue;
     } else {
-      if (zo) hipLaunchKernelGGL((k_bp_lane2<T, 1, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      else hipLaunchKernelGGL((k_bp_lane2<T, 1, false>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      with_bp_zo(zo, [&](auto z) {
+        hipLaunchKernelGGL((k_bp_lane2<T, 1, decltype(z)::value>), grid, block, 0, st, b, p, f, lane_dev_fence());
+      });
     }
     if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
-      hipLaunchKernelGGL((k_bp_lane2<T, 1, false, true>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
+      hipLaunchKernelGGL((k_bp_lane2<T, 1, 0, true>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
     return hipGetLastError();
   }
   switch (lane_wpb()) {
@@ -1539,9 +1593,9 @@ hipError_t launch_psk_bandpass_fixup(const PskBuffers& b, const PskParams& p, co
   if (f.nt != 9) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((b.n_streams + 63) / 64)), block(128);
   switch (b.dtype) {
-    case kF32: hipLaunchKernelGGL((k_bp_lane2<float, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
-    case kF64: hipLaunchKernelGGL((k_bp_lane2<double, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
-    case kI16: hipLaunchKernelGGL((k_bp_lane2<int16_t, 1, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
+    case kF32: hipLaunchKernelGGL((k_bp_lane2<float, 1, 0, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
+    case kF64: hipLaunchKernelGGL((k_bp_lane2<double, 1, 0, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
+    case kI16: hipLaunchKernelGGL((k_bp_lane2<int16_t, 1, 0, true>), grid, block, 0, st, b, p, f, lane_dev_fence()); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
