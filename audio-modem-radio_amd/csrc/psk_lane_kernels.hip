@@ -20,13 +20,15 @@
 // device (api.cpp) -- several batches at once, or big batches.
 //
 // Intermediates not written to HBM (checkpoint + recompute):
-//   * band-pass (k_bp_lane): the forward pass keeps the filter state at the
-//     start of every kBpT-sample tile (8 doubles); the backward pass re-runs
-//     each tile forward from its checkpoint into registers and filters it
-//     backward from there -- the forward output s1 (2 x 8 B/sample of HBM
-//     traffic in the round-1 kernels) becomes 4 B/sample of re-read input
-//     plus 4 B/sample of checkpoints.
-//   * low-pass (k_lp_lane): the same over f with kLpT-sample tiles (4
+//   * band-pass (k_bp_lane2, two waves per group of 64 streams): the forward
+//     pass keeps the filter state at the start of every kBpT-sample tile (8
+//     doubles); then one wave re-runs each tile forward from its checkpoint
+//     into LDS while the other filters the tile before it backward out of LDS
+//     -- the forward output s1 (2 x 8 B/sample of HBM traffic in the round-1
+//     kernels) becomes 4 B/sample of re-read input plus 4 B/sample of
+//     checkpoints.
+//   * low-pass (k_lp_lane): the same in one wave over f with kLpT-sample
+//     tiles, each re-run into registers and filtered backward from there (4
 //     doubles per component) -- the complex forward output s3 (2 x 16
 //     B/sample) becomes a second read of f (8 B/sample, mostly L2: the re and
 //     im waves of the same streams run on one XCD) plus 2 B/sample of
@@ -41,7 +43,6 @@
 // A re-run tile executes exactly the operations the forward pass executed,
 // from exactly the same state, so it reproduces its outputs bit for bit.
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 #include <utility>
@@ -55,7 +56,16 @@ namespace amr {
 
 constexpr int kBpT = 32;    // band-pass checkpoint tile (samples)
 constexpr int kLpT = 40;     // low-pass checkpoint tile: a multiple of sps 5 / 10 / 20 (static symbol slots)
-constexpr int kLpT2 = 20;    // the same for the role-split low-pass (LDS: 2 components x 2 buffers x tile)
+// The static symbol slots number tile t's symbols from t * (kLpT / SPS) -
+// first / SPS, which is valid (>= 0 from the first recomputed tile on) while
+// first is at most the tile length; a plan with a later first sample takes the
+// generic kernel.  20 is conservative for the 40-sample tile; it decides which
+// low-pass a plan gets (amr_psk_plan_last_lowpass), so it keeps its value.
+constexpr int kLpStaticFirstMax = 20;
+// s3 reserves a checkpoint row per 20 samples: twice what kLpT needs.  The
+// plans' scratch totals are pinned to the byte (amr_psk_plan_scratch_bytes);
+// shrinking the reservation is a footprint change for a change of its own.
+constexpr int kLpCkReserveT = 20;
 
 // (the DF-II-T step functions df2t_step / df2t_step_zo / lp_step: psk_common.h)
 
@@ -93,234 +103,38 @@ int64_t psk_lane_bp_scratch_doubles(int64_t n_streams, int64_t n, int pad) {
 }
 int64_t psk_lane_lp_scratch_doubles(int64_t n_streams, int64_t n, int pad) {
   const int64_t g = (n_streams + 63) / 64;
-  return 2 * g * ((n / kLpT2) * 4 + 2 * (kLpT + pad)) * 64;   // the smaller tile's checkpoints, the larger edges
+  return 2 * g * ((n / kLpCkReserveT) * 4 + lp_lane_edge_cap(pad)) * 64;
 }
 
 // ---------------------------------------------------------------------------
-// band-pass: lane = stream, wave = 64 streams.  Coefficients are wave-uniform
-// (kernel arguments in SGPRs).  s1 = [G][nt][8][64] checkpoints, then
-// [G][edge][64] tail outputs.
-template <typename T, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_bp_lane(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
-  constexpr int TB = kBpT;
-  constexpr int PER = 16 / (int)sizeof(T);      // samples per 16-B load
-  constexpr int NL = TB / PER;                  // 16-B loads per tile
-  static_assert(TB % PER == 0 && TB % 2 == 0, "tile = whole loads and whole pairs");
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (w * 64 >= buf.n_streams) return;          // wave-uniform
-  const int64_t last = buf.n_streams - 1;
-  const int64_t s = w * 64 + lane;
-  const T* __restrict__ x = reinterpret_cast<const T*>(buf.x) + (s < last ? s : last) * buf.x_stride;
-  const uint8_t* __restrict__ xb = reinterpret_cast<const uint8_t*>(x);
-  const int64_t n = p.n, n2 = (n + 1) >> 1;
-  const int pad = p.pad1;
-  const int64_t nt = n / TB;
-  const int64_t G = (buf.n_streams + 63) / 64;
-  const int64_t ecap = bp_lane_edge_cap(pad);
-  double* __restrict__ ck = buf.s1 + (size_t)w * nt * 8 * 64 + lane;
-  double* __restrict__ eb = buf.s1 + (size_t)G * nt * 8 * 64 + (size_t)w * ecap * 64 + lane;
-  // f = s2 in f_index layout: this lane's pair m at fo + m*64
-  double* __restrict__ fo = buf.s2 + (size_t)(w * 2 + (lane >> 5)) * n2 * 64 + (lane & 31) * 2;
-
-  auto load_tile = [&](int64_t t, v4u (&r)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) r[k] = *reinterpret_cast<const v4u*>(xb + (size_t)t * TB * sizeof(T) + k * 16);
-  };
-  auto tile_x = [&](const v4u (&r)[NL], int k) -> double {
-    T v[PER];
-    __builtin_memcpy(v, &r[k / PER], 16);
-    return In<T>::cvt(v[k % PER]);
-  };
-
-  // ---- forward pass: pads + tiles (checkpoints only) + tail (edge) --------
-  double z[8];
-  const OddExt<T> ox(x, buf.edge, s < last ? s : last, n, pad);
-  {
-    const double e0 = ox.left(0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = f.zi[j] * e0;
-  }
-  for (int jj = 0; jj < pad; ++jj) (void)df2t_step<8>(z, f, ox.left(jj));
-  v4u xr[NL];
-  if (nt > 0) load_tile(0, xr);
-  for (int64_t t = 0; t < nt; ++t) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ck[(t * 8 + j) * 64] = z[j];
-    v4u cur[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) cur[k] = xr[k];
-    load_tile(t + 1 < nt ? t + 1 : t, xr);      // next tile in flight during this one
-#pragma unroll
-    for (int k = 0; k < TB; ++k) (void)df2t_step<8>(z, f, tile_x(cur, k));
-  }
-  const int64_t i_tail = nt * TB;
-  int ne = 0;
-  for (int64_t i = i_tail; i < n; ++i) eb[(ne++) * 64] = df2t_step<8>(z, f, In<T>::cvt(x[i]));
-  double ylast = 0.0;
-  for (int jj = 0; jj < pad; ++jj) {
-    ylast = df2t_step<8>(z, f, ox.right(jj));
-    eb[(ne++) * 64] = ylast;
-  }
-  lane_pass_fence(dev_fence);                   // checkpoints / edge: re-read below by this wave alone
-
-  // ---- backward pass ------------------------------------------------------
-  double zb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) zb[j] = f.zi[j] * ylast;
-  for (int e = ne - 1; e >= 0; --e) {
-    const double y = df2t_step<8>(zb, f, eb[e * 64]);
-    const int64_t i = i_tail + e;
-    if (i < n) fo[(i >> 1) * 64 + (i & 1)] = y;
-  }
-  if (nt > 0) {
-    load_tile(nt - 1, xr);
-    double cn[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) cn[j] = ck[((nt - 1) * 8 + j) * 64];
-    for (int64_t t = nt - 1; t >= 0; --t) {
-      double zf[8];
-      v4u cur[NL];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) zf[j] = cn[j];
-#pragma unroll
-      for (int k = 0; k < NL; ++k) cur[k] = xr[k];
-      const int64_t tp = t > 0 ? t - 1 : 0;     // the next (lower) tile's input and checkpoint in flight
-      load_tile(tp, xr);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cn[j] = ck[(tp * 8 + j) * 64];
-      double yt[TB];
-#pragma unroll
-      for (int k = 0; k < TB; ++k) yt[k] = df2t_step<8>(zf, f, tile_x(cur, k));
-      double* const fp = fo + (size_t)(t * (TB / 2)) * 64;
-#pragma unroll
-      for (int k = TB - 1; k >= 1; k -= 2) {
-        const double y1 = df2t_step<8>(zb, f, yt[k]);
-        const double y0 = df2t_step<8>(zb, f, yt[k - 1]);
-        *reinterpret_cast<double2*>(fp + (k >> 1) * 64) = make_double2(y0, y1);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// The band-pass forward pass of one group (lane = stream): pads + tiles
-// (checkpoint at the start of every tile, no output) + tail (edge outputs);
-// the zero-tap detector flags a stream it cannot vouch for.  Used by
-// k_bp_lane2's forward role and, on its own, by k_bp_fwd.
-template <typename T, int ZO>
-__device__ __forceinline__ void bp_forward_pass(const PskBuffers& buf, const PskParams& p, const Iir& f, int64_t w,
-                                                int lane) {
-  constexpr int TB = kBpT;
-  constexpr int PER = 16 / (int)sizeof(T);
-  constexpr int NL = TB / PER;
-  const int64_t last = buf.n_streams - 1;
-  const int64_t s = w * 64 + lane;
-  const T* __restrict__ x = reinterpret_cast<const T*>(buf.x) + (s < last ? s : last) * buf.x_stride;
-  const uint8_t* __restrict__ xb = reinterpret_cast<const uint8_t*>(x);
-  const int64_t n = p.n;
-  const int pad = p.pad1;
-  const int64_t nt = n / TB;
-  const int64_t G = (buf.n_streams + 63) / 64;
-  const int64_t ecap = bp_lane_edge_cap(pad);
-  const int64_t i_tail = nt * TB;
-  double* __restrict__ ck = buf.s1 + (size_t)w * nt * 8 * 64 + lane;
-  double* __restrict__ eb = buf.s1 + (size_t)G * nt * 8 * 64 + (size_t)w * ecap * 64 + lane;
-  auto load_tile = [&](int64_t t, v4u (&r)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) r[k] = *reinterpret_cast<const v4u*>(xb + (size_t)t * TB * sizeof(T) + k * 16);
-  };
-  auto tile_x = [&](const v4u (&r)[NL], int k) -> double {
-    T v[PER];
-    __builtin_memcpy(v, &r[k / PER], 16);
-    return In<T>::cvt(v[k % PER]);
-  };
-  double z[8];
-  float acc = __builtin_inff();
-  const OddExt<T> ox(x, buf.edge, s < last ? s : last, n, pad);
-  {
-    const double e0 = ox.left(0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = f.zi[j] * e0;
-  }
-  for (int jj = 0; jj < pad; ++jj) {
-    const double y = bp_step<ZO>(z, f, ox.left(jj), acc);
-    bp_watch<ZO>(acc, y, y);
-  }
-  v4u xr[NL];
-  if (nt > 0) load_tile(0, xr);
-  for (int64_t t = 0; t < nt; ++t) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ck[(t * 8 + j) * 64] = z[j];
-    v4u cur[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) cur[k] = xr[k];
-    load_tile(t + 1 < nt ? t + 1 : t, xr);
-#pragma unroll
-    for (int k = 0; k < TB; k += 2) {
-      const double y0 = bp_step<ZO>(z, f, tile_x(cur, k), acc);
-      const double y1 = bp_step<ZO>(z, f, tile_x(cur, k + 1), acc);
-      bp_watch<ZO>(acc, y0, y1);
-    }
-  }
-  int e = 0;
-  for (int64_t i = i_tail; i < n; ++i) {
-    const double y = bp_step<ZO>(z, f, In<T>::cvt(x[i]), acc);
-    bp_watch<ZO>(acc, y, y);
-    eb[(e++) * 64] = y;
-  }
-  for (int jj = 0; jj < pad; ++jj) {
-    const double y = bp_step<ZO>(z, f, ox.right(jj), acc);
-    bp_watch<ZO>(acc, y, y);
-    eb[(e++) * 64] = y;
-  }
-  if (bp_bad<ZO>(acc, z) && s <= last) atomicOr(&buf.bp_flags[s], 1);
-}
-
-// band-pass forward pass alone, wave = group (AMR_BP_PREFWD): k_bp_lane2<...,
-// PRE> then runs only the re-run / backward roles.  The forward pass no
-// longer holds an idle backward wave and its LDS for half the band-pass's
-// life.
-template <typename T, int ZO>
-__global__ __launch_bounds__(256) void k_bp_fwd(PskBuffers buf, PskParams p, Iir f) {
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (w * 64 >= buf.n_streams) return;          // wave-uniform
-  bp_forward_pass<T, ZO>(buf, p, f, w, lane);
-}
-
-// ---------------------------------------------------------------------------
-// band-pass, role-split: two waves per group of 64 streams (GPB groups per
-// workgroup).  Wave 0 runs the forward pass (checkpoints + tail edge) while
-// wave 1 waits; then, tile by tile from the end, wave 0 re-runs tile t-1
-// forward from its checkpoint into one LDS buffer while wave 1 filters tile t
-// backward out of the other buffer and stores f -- the backward pass and the
-// re-run overlap, so the kernel takes two passes of latency instead of three
-// and a batch has twice the waves.  One workgroup barrier per tile.
-// FIXUP (with ZO false): the full-tap re-run of the groups the zero-tap
-// launch flagged; a workgroup whose group has no flagged stream returns
-// before its first barrier (2-wave, 108-VGPR workgroups: they find room
-// beside the resident band-pass / low-pass waves, where the one-wave kernel's
-// 168-VGPR four-wave workgroups waited up to 15 ms at 8192 streams).
-// CK = 2 (AMR_BP_CK=2): a checkpoint every 2 tiles (64 samples: half the
-// checkpoint bytes) while the LDS hand-off stays at one 32-sample tile, so
-// the workgroup keeps its 64 KiB and two fit a CU.  The re-run role then
-// reaches the second tile of a pair by first re-running the pair's first
-// tile without outputs (1.5x its steps), holding the pair's inputs in
-// registers (one more tile of them) -- bit for bit the same outputs.
+// band-pass: lane = stream, two waves per group of 64 streams (GPB groups per
+// workgroup).  Coefficients are wave-uniform (kernel arguments in SGPRs).
+// s1 = [G][nt][8][64] checkpoints, then [G][edge][64] tail outputs.
+// Wave 0 runs the forward pass (a checkpoint at the start of every tile, no
+// output; the tail's edge outputs) while wave 1 waits; then, tile by tile from
+// the end, wave 0 re-runs tile t-1 forward from its checkpoint into one LDS
+// buffer while wave 1 filters tile t backward out of the other buffer and
+// stores f -- the backward pass and the re-run overlap, so the kernel takes
+// two passes of latency instead of three.  One workgroup barrier per tile.
+// Two forms are instantiated:
+//   * GPB = 2, any ZO: the band-pass launch, two groups per 256-thread
+//     workgroup.
+//   * GPB = 1, FIXUP (every tap, float64 f): the re-run of the groups the
+//     zero-tap launch (or the float32 hand-off's margin check) flagged; a
+//     workgroup whose group has no flagged stream returns before its first
+//     barrier (2-wave, 108-VGPR workgroups find room beside the resident
+//     band-pass / low-pass waves).
 // F32F (PskBuffers::f32f): f is stored rounded to float32 into the first half
 // of the group's s2 slot (the f64 layout's element order, float elements),
 // and each stream's max |f| (bits: NaN / inf dominate) into buf.fpeak.
 // NT: which access classes go non-temporal (psk_common.h: kNtFStore the f
-// stores, kNtCk the checkpoints and edge rows, kNtX the x tiles); 0 for the
-// PRE, CK = 2 and F32F variants.
-template <typename T, int GPB, int ZO, bool FIXUP = false, bool PRE = false, int CK = 1, bool F32F = false, int NT = 0>
+// stores, kNtCk the checkpoints and edge rows, kNtX the x tiles); 0 with F32F.
+template <typename T, int GPB, int ZO, bool FIXUP = false, bool F32F = false, int NT = 0>
 __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParams p, Iir f, int dev_fence) {
-  static_assert(NT == 0 || (!PRE && CK == 1 && !F32F), "cache policies: the default paths only");
+  static_assert(FIXUP ? GPB == 1 && !ZO && !F32F : GPB == 2,
+                "two groups per workgroup, or the fix-up pass: one group, every tap, float64 f");
+  static_assert(NT == 0 || !F32F, "cache policies: the float64 paths only");
   constexpr bool NTF = (NT & kNtFStore) != 0, NTC = (NT & kNtCk) != 0, NTX = (NT & kNtX) != 0;
-  static_assert(!(FIXUP && PRE), "the fix-up pass runs its own forward pass");
-  static_assert(!(F32F && FIXUP), "the fix-up pass writes float64 f");
-  static_assert(CK == 1 || (CK == 2 && !PRE), "64-sample checkpoints: the kernel's own forward pass");
   constexpr int TB = kBpT;
   constexpr int PER = 16 / (int)sizeof(T);
   constexpr int NL = TB / PER;
@@ -334,7 +148,6 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
   const int64_t last = buf.n_streams - 1;
   const int64_t s = w * 64 + lane;
   if constexpr (FIXUP) {
-    static_assert(GPB == 1 && !ZO, "the fix-up pass: one group per workgroup, every tap");
     if (!active) return;                        // workgroup-uniform (one group)
     if (!__syncthreads_or(s <= last && buf.bp_flags[s] != 0)) return;   // nothing flagged in this group
   }
@@ -364,10 +177,11 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
     return In<T>::cvt(v[k % PER]);
   };
 
-  if (!PRE && role == 0 && active) {
+  if (role == 0 && active) {
     // ---- forward pass: pads + tiles (checkpoints only) + tail (edge) ------
-    // (the same steps as bp_forward_pass, written out: through the device
-    // function the compiler kept 238 VGPRs live here against 113)
+    // (written out here, not a device function: through one the compiler
+    // kept 238 VGPRs live against 113); the zero-tap detector flags a stream
+    // it cannot vouch for
     double z[8];
     float acc = __builtin_inff();
     const OddExt<T> ox(x, buf.edge, s < last ? s : last, n, pad);
@@ -383,10 +197,8 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
     v4u xr[NL];
     if (nt > 0) load_tile(0, xr);
     for (int64_t t = 0; t < nt; ++t) {
-      if (t % CK == 0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) st_pol<NTC>(&ck[((t / CK) * 8 + j) * 64], z[j]);
-      }
+      for (int j = 0; j < 8; ++j) st_pol<NTC>(&ck[(t * 8 + j) * 64], z[j]);
       v4u cur[NL];
 #pragma unroll
       for (int k = 0; k < NL; ++k) cur[k] = xr[k];
@@ -417,63 +229,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
   }
   __syncthreads();
 
-  if (role == 0 && CK == 2) {
-    // ---- re-run tiles nt-1 ... 0 into LDS, checkpoints every 2 tiles -------
-    // pair c = tiles (2c, 2c+1) from checkpoint c; tile 2c+1 re-runs tile 2c
-    // first (no outputs).  Registers: the pair's inputs (xa, xb), the next
-    // pair's arriving one tile ahead (xbn at the odd tile, xan at the even).
-    v4u xa[NL], xb[NL], xan[NL], xbn[NL];
-    double cc[8], ccn[8];
-    if (active && nt > 0) {
-      const int64_t c = (nt - 1) >> 1;
-      load_tile(2 * c, xa);
-      if (2 * c + 1 < nt) load_tile(2 * c + 1, xb);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cc[j] = ck[(c * 8 + j) * 64];
-    }
-    for (int64_t it = 0; it <= nt; ++it) {
-      const int64_t t = nt - 1 - it;
-      if (active && t >= 0) {
-        const int64_t c = t >> 1, cp = c > 0 ? c - 1 : 0;
-        double zf[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) zf[j] = cc[j];
-        double2 (*ybuf)[64] = yb[gi][it & 1];
-        float dummy = 0.0f;                     // the re-run repeats checked steps: no detector
-        if (t & 1) {
-          load_tile(2 * cp + 1, xbn);           // the next pair's second tile and checkpoint
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ccn[j] = ck[(cp * 8 + j) * 64];
-#pragma unroll
-          for (int k = 0; k < TB; ++k) (void)bp_step<ZO>(zf, f, tile_x(xa, k), dummy);
-#pragma unroll
-          for (int k = 0; k < TB; k += 2) {
-            const double y0 = bp_step<ZO>(zf, f, tile_x(xb, k), dummy);
-            const double y1 = bp_step<ZO>(zf, f, tile_x(xb, k + 1), dummy);
-            ybuf[k >> 1][lane] = make_double2(y0, y1);
-          }
-        } else {
-          if (2 * c + 1 >= nt) {                // a top pair of one tile: nothing was prefetched for the next
-            load_tile(2 * cp + 1, xbn);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ccn[j] = ck[(cp * 8 + j) * 64];
-          }
-          load_tile(2 * cp, xan);
-#pragma unroll
-          for (int k = 0; k < TB; k += 2) {
-            const double y0 = bp_step<ZO>(zf, f, tile_x(xa, k), dummy);
-            const double y1 = bp_step<ZO>(zf, f, tile_x(xa, k + 1), dummy);
-            ybuf[k >> 1][lane] = make_double2(y0, y1);
-          }
-#pragma unroll
-          for (int k = 0; k < NL; ++k) { xa[k] = xan[k]; xb[k] = xbn[k]; }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) cc[j] = ccn[j];
-        }
-      }
-      __syncthreads();
-    }
-  } else if (role == 0) {
+  if (role == 0) {
     // ---- re-run tiles nt-1, nt-2, ... 0 forward into LDS --------------------
     v4u xr[NL];
     double cn[8];
@@ -568,11 +324,9 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 
 // ---------------------------------------------------------------------------
 // low-pass: lane = stream, wave = 64 streams x ONE component (so the LO
-// multiplier is wave-uniform).  WPB == 1: blocks b and b+8 are the re and im
-// waves of the same streams and land on the same XCD (blocks are dealt to the
-// 8 XCDs round-robin); WPB >= 2: waves (2i, 2i+1) of a block are the re and
-// im waves of one stream group, on one CU -- either way the second read of f
-// is a cache hit (PMC: f is read from HBM once per pass).
+// multiplier is wave-uniform), four waves per workgroup: waves (2i, 2i+1) of
+// a block are the re and im waves of one stream group, on one CU, so the
+// second read of f is a cache hit (PMC: f is read from HBM once per pass).
 // Mixer and detector exactly as K2q/K3q (psk_kernels.hip): bb[0] in numpy's
 // full complex-multiply form, every other sample f*lo_c (equal whenever it
 // is not a zero, and a zero is flagged); min over |hi words| of every input
@@ -598,7 +352,7 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 #ifndef AMR_LP_REGION_SYMS
 #define AMR_LP_REGION_SYMS 8     // fused slicer: symbols per slicing region at most (a power of two >= TL / sps)
 #endif
-// FUSE (static symbol slots, WPB >= 2): the slicer runs inside the backward
+// FUSE (static symbol slots): the slicer runs inside the backward
 // pass.  Both component waves of a group park their symbol samples in an LDS
 // ring (16 slots: a region -- the tail, RT tiles, the head -- holds at most 8
 // symbols, and two consecutive regions never share a slot), meet at one
@@ -616,15 +370,16 @@ __global__ __launch_bounds__(128 * GPB) void k_bp_lane2(PskBuffers buf, PskParam
 // boundary -- QPSK ||di| - |dr||, BPSK |dr| against sqrt2 E (|s0|_1 + |s1|_1 +
 // E) -- into flags and bp_flags, and the fix-up band-pass, K3x and K4a redo
 // those streams exactly.
-// NT (four-wave workgroups, float64 f): which access classes go non-temporal
+// NT (float64 f): which access classes go non-temporal
 // (psk_common.h: kNtFLoad the f loads, kNtCk the checkpoints and edges,
 // kNtWords the fused slicer's word stores).
-template <int SPS, int FM, int WPB, bool FUSE = false, bool F32F = false, int NT = 0>
-__global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lane(PskBuffers buf, PskParams p, Iir f,
-                                                                                 int dev_fence) {
-  static_assert(NT == 0 || (WPB == 4 && !F32F), "cache policies: the default paths only");
+template <int SPS, int FM, bool FUSE = false, bool F32F = false, int NT = 0>
+__global__ __launch_bounds__(256, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lane(PskBuffers buf, PskParams p, Iir f,
+                                                                            int dev_fence) {
+  constexpr int WPB = 4;                        // waves per workgroup: two groups x (re, im)
+  static_assert(NT == 0 || !F32F, "cache policies: the float64 paths only");
   constexpr bool NTF = (NT & kNtFLoad) != 0, NTC = (NT & kNtCk) != 0, NTW = (NT & kNtWords) != 0;
-  static_assert(!FUSE || (SPS > 0 && WPB >= 2), "fused slicing: static slots, both components in one workgroup");
+  static_assert(!FUSE || SPS > 0, "fused slicing: static slots");
   static_assert(!F32F || FUSE, "the float32 hand-off's margin check runs in the fused slicer");
   using FV = typename std::conditional<F32F, float2, double2>::type;
   constexpr int TL = kLpT;
@@ -645,16 +400,8 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
   __shared__ double sring[FUSE ? WPB : 1][NSL][64];   // FUSE: symbol samples k at slot k & (NSL - 1)
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int64_t w;
-  int comp;
-  if constexpr (WPB == 1) {
-    const int64_t bx = blockIdx.x, kx = bx >> 3;
-    w = (kx >> 1) * 8 + (bx & 7);
-    comp = (int)(kx & 1);
-  } else {
-    w = (int64_t)blockIdx.x * (WPB / 2) + (wv >> 1);
-    comp = wv & 1;
-  }
+  const int64_t w = (int64_t)blockIdx.x * (WPB / 2) + (wv >> 1);
+  const int comp = wv & 1;
   const int64_t n = p.n, n2 = (n + 1) >> 1;
   const int pad = p.pad2;
   const int64_t nt = n / TL;
@@ -929,7 +676,7 @@ __global__ __launch_bounds__(64 * WPB, SPS > 0 ? AMR_LP_WAVES : 1) void k_lp_lan
 // 0-31 their re and lanes 32-63 their im component (lane l and l + 32 are one
 // stream).  A group of 64 streams is still two waves -- split by stream half
 // (the two 512-B runs of f_index) instead of by component -- and a workgroup
-// four waves = two groups, the grid and placement of k_lp_lane<.., 4>.
+// four waves = two groups, the grid and placement of k_lp_lane.
 // Per lane the arithmetic is k_lp_lane's, in its order: the mixer, lp_step,
 // the tiny_min3 detector, the class checks, forward pass / re-run / backward
 // pass.  What changes is what the waves share:
@@ -1199,245 +946,7 @@ __global__ __launch_bounds__(256, AMR_LP_WAVES) void k_lp_lane_h(PskBuffers buf,
 }
 
 // ---------------------------------------------------------------------------
-// low-pass, role-split: four waves per group of 64 streams -- (re, im) x
-// (forward / re-run, backward).  The forward waves run the forward pass
-// (checkpoints every TL2 samples, head / tail edges, the input/output zero
-// detector) while the backward waves wait; then tile by tile from the end the
-// forward waves re-run tile t-1 into an LDS buffer while the backward waves
-// filter tile t out of the other one and write the symbol samples.  Two
-// passes of latency instead of three.  Same arithmetic and detector as
-// k_lp_lane; TL2 = 20 keeps the LDS of a group at 40 KB.
-template <int SPS, int FM, int TL2>
-__global__ __launch_bounds__(256) void k_lp_lane2(PskBuffers buf, PskParams p, Iir f) {
-  constexpr int TL = TL2;
-  constexpr int CH = TL % 8 == 0 ? 8 : 4;       // samples per f chunk
-  constexpr int NCH = TL / CH, HC = CH / 2;
-  static_assert(TL % CH == 0 && TL <= 64, "tile = whole chunks; one LO value per lane");
-  static_assert(SPS == 0 || (TL % SPS == 0 && FM < SPS), "static symbol slots");
-  __shared__ __attribute__((aligned(16))) double lo_lds[2][2][TL];              // [comp][buf]
-  __shared__ __attribute__((aligned(16))) double2 yb[2][2][TL / 2][64];        // [comp][buf][pair][lane]
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int comp = wv & 1, role = wv >> 1;
-  const int64_t w = blockIdx.x;
-  if (w * 64 >= buf.n_streams) return;          // block-uniform: no barrier is skipped by part of a block
-  const int64_t s = w * 64 + lane;
-  const int64_t n = p.n, n2 = (n + 1) >> 1;
-  const int pad = p.pad2;
-  const int64_t nt = n / TL;
-  const int64_t G = (buf.n_streams + 63) / 64;
-  const int64_t wc = w * 2 + comp;
-  const int64_t ecap = 2 * (TL + pad);
-  double* __restrict__ ck = buf.s3 + (size_t)wc * nt * 4 * 64 + lane;
-  double* __restrict__ eh = buf.s3 + (size_t)2 * G * nt * 4 * 64 + (size_t)wc * ecap * 64 + lane;
-  double* __restrict__ et = eh + (size_t)(pad + TL) * 64;
-  const double* __restrict__ fl = buf.s2 + (size_t)(w * 2 + (lane >> 5)) * n2 * 64 + (lane & 31) * 2;
-  const double* __restrict__ lov = buf.lo2 + (size_t)comp * n;
-  CDouble* const loc = (CDouble*)(buf.lo2 + (size_t)comp * n);
-  CDouble* const lo4 = (CDouble*)(buf.lo) + 2 * comp;
-  auto F = [&](int64_t i) { return fl[(i >> 1) * 64 + (i & 1)]; };
-  auto Xm = [&](int64_t i) { return F(i) * loc[i]; };
-  auto load_chunk = [&](int64_t t, int c, double2 (&r)[HC]) {
-    const double2* fp = reinterpret_cast<const double2*>(fl + (size_t)(t * (TL / 2) + c * HC) * 64);
-#pragma unroll
-    for (int k = 0; k < HC; ++k) r[k] = fp[k * 32];
-  };
-  auto load_lo = [&](int64_t t) -> double { return lov[t * TL + (lane < TL ? lane : 0)]; };
-  auto put_lo = [&](int64_t t, double v) {
-    if (lane < TL) lo_lds[comp][t & 1][lane] = v;
-  };
-  auto chunk_e = [&](int64_t t, int c, const double2 (&fv)[HC], double (&e)[CH]) {
-    const double2* lp = reinterpret_cast<const double2*>(&lo_lds[comp][t & 1][c * CH]);
-#pragma unroll
-    for (int k = 0; k < HC; ++k) {
-      const double2 l = lp[k];
-      e[2 * k] = fv[k].x * l.x;
-      e[2 * k + 1] = fv[k].y * l.y;
-    }
-  };
-  const int64_t nh = n < TL ? n : TL;
-  const int64_t i_tail = nt >= 1 ? nt * TL : nh;
-  const int ne = (int)(n - i_tail) + pad;
-
-  if (role == 0) {
-    // ---- forward pass (as k_lp_lane) ----------------------------------------
-    double z[4];
-    float acc = __builtin_inff();
-    bool bad = false;
-    const double x0 = F(0) * lo4[0] + lo4[1];
-    const double xl = Xm(n - 1);
-    bad |= __builtin_amdgcn_class(x0, kClsX);
-    const double e0 = 2.0 * x0 - Xm(pad);
-    bad |= __builtin_amdgcn_class(e0, kClsY);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = f.zi[j] * e0;
-    for (int jj = 0; jj < pad; ++jj) {
-      const double e = 2.0 * x0 - Xm(pad - jj);
-      const double y = lp_step(z, f, e);
-      acc = tiny_min3(acc, e, y);
-      eh[jj * 64] = y;
-    }
-    for (int64_t i = 0; i < nh; ++i) {
-      const double e = i == 0 ? x0 : Xm(i);
-      const double y = lp_step(z, f, e);
-      acc = tiny_min3(acc, i == 0 ? y : e, y);
-      eh[(pad + i) * 64] = y;
-    }
-    double2 ring[NCH][HC];
-    if (nt > 1) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) load_chunk(1, c, ring[c]);
-      put_lo(1, load_lo(1));
-    }
-    for (int64_t t = 1; t < nt; ++t) {
-      const int64_t tn = t + 1 < nt ? t + 1 : t;
-      const double lon = load_lo(tn);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ck[(t * 4 + j) * 64] = z[j];
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        double2 fv[HC];
-#pragma unroll
-        for (int k = 0; k < HC; ++k) fv[k] = ring[c][k];
-        load_chunk(tn, c, ring[c]);
-        double e[CH];
-        chunk_e(t, c, fv, e);
-#pragma unroll
-        for (int k = 0; k < CH; k += 2) {
-          const double y0 = lp_step(z, f, e[k]);
-          const double y1 = lp_step(z, f, e[k + 1]);
-          acc = tiny_min3(acc, e[k], e[k + 1]);
-          acc = tiny_min3(acc, y0, y1);
-        }
-      }
-      put_lo(tn, lon);
-    }
-    int ee = 0;
-    for (int64_t i = i_tail; i < n; ++i) {
-      const double e = Xm(i);
-      const double y = lp_step(z, f, e);
-      acc = tiny_min3(acc, e, y);
-      et[(ee++) * 64] = y;
-    }
-    for (int jj = 0; jj < pad; ++jj) {
-      const double e = 2.0 * xl - Xm(n - 2 - jj);
-      const double y = lp_step(z, f, e);
-      acc = tiny_min3(acc, e, y);
-      et[(ee++) * 64] = y;
-    }
-    bad |= !(acc >= kTinyHi);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(z[j]);
-    if (bad && s < buf.n_streams) atomicOr(&buf.flags[s], 1);
-    __threadfence();                            // checkpoints + edges: read by both roles
-    __syncthreads();
-
-    // ---- re-run tiles nt-1 .. 1 forward into LDS -----------------------------
-    double cn[4];
-    if (nt > 1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cn[j] = ck[((nt - 1) * 4 + j) * 64];
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) load_chunk(nt - 1, c, ring[c]);
-      put_lo(nt - 1, load_lo(nt - 1));
-    }
-    for (int64_t it = 0; it < nt; ++it) {       // it = nt-1 is the backward waves' last tile: barrier only
-      const int64_t t = nt - 1 - it;
-      if (t >= 1) {
-        double zf[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) zf[j] = cn[j];
-        const int64_t tp = t > 1 ? t - 1 : 1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cn[j] = ck[(tp * 4 + j) * 64];
-        const double lop = load_lo(tp);
-        double2 (*ybuf)[64] = yb[comp][it & 1];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          double2 fv[HC];
-#pragma unroll
-          for (int k = 0; k < HC; ++k) fv[k] = ring[c][k];
-          load_chunk(tp, c, ring[c]);
-          double e[CH];
-          chunk_e(t, c, fv, e);
-#pragma unroll
-          for (int k = 0; k < CH; k += 2) {
-            const double y0 = lp_step(zf, f, e[k]);
-            const double y1 = lp_step(zf, f, e[k + 1]);
-            ybuf[(c * CH + k) >> 1][lane] = make_double2(y0, y1);
-          }
-        }
-        put_lo(tp, lop);
-      }
-      __syncthreads();
-    }
-  } else {
-    __syncthreads();                            // the forward pass is done
-    const int64_t S = p.n_sym, first = p.first, sps = p.sps;
-    double* __restrict__ symp = buf.s1 + sym_index(s, S, 0, comp);
-    auto sym_out = [&](int64_t i, double y) {
-      if (i >= first && (i - first) % sps == 0) symp[((i - first) / sps) * 64] = y;
-    };
-    float accb = __builtin_inff();
-    double zb[4];
-    const double ylast = et[(ne - 1) * 64];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) zb[j] = f.zi[j] * ylast;
-    for (int e = ne - 1; e >= 0; --e) {
-      const double y = lp_step(zb, f, et[e * 64]);
-      accb = tiny_min3(accb, y, y);
-      const int64_t i = i_tail + e;
-      if (i < n) sym_out(i, y);
-    }
-    // the forward waves meet nt barriers in their re-run loop: tile nt-1 is in
-    // buffer 0 after the first (none at all when nt == 0)
-    if (nt >= 1) __syncthreads();
-    const int64_t q0 = SPS > 0 ? first / SPS : 0;
-    for (int64_t it = 1; it < nt; ++it) {
-      const int64_t t = nt - it;
-      const double2 (*ybuf)[64] = yb[comp][(it - 1) & 1];
-#pragma unroll
-      for (int k = TL - 1; k >= 1; k -= 2) {
-        const double2 yy = ybuf[k >> 1][lane];
-        const double y1 = lp_step(zb, f, yy.y);
-        const double y0 = lp_step(zb, f, yy.x);
-        accb = tiny_min3(accb, y1, y0);
-        if constexpr (SPS > 0) {
-          if (k % SPS == FM) symp[(t * (TL / SPS) + (k - FM) / SPS - q0) * 64] = y1;
-          if ((k - 1) % SPS == FM) symp[(t * (TL / SPS) + (k - 1 - FM) / SPS - q0) * 64] = y0;
-        } else {
-          sym_out(t * TL + k, y1);
-          sym_out(t * TL + k - 1, y0);
-        }
-      }
-      __syncthreads();
-    }
-    for (int e = pad + (int)nh - 1; e >= 0; --e) {
-      const double y = lp_step(zb, f, eh[e * 64]);
-      accb = tiny_min3(accb, y, y);
-      const int64_t i = e - pad;
-      if (i >= 0) sym_out(i, y);
-    }
-    bool bad = !(accb >= kTinyHi);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bad |= !__builtin_isfinite(zb[j]);
-    if (bad && s < buf.n_streams) atomicOr(&buf.flags[s], 1);
-  }
-}
-
-// ---------------------------------------------------------------------------
 // host-side launchers (api.cpp)
-static int lane_wpb() {
-  // waves per workgroup of the lane kernels: AMR_LANE_WPB=1/2/4 (default 4:
-  // with 16 batches in flight, 4-wave workgroups ran 4.85 ms/step against
-  // 5.82 for one-wave workgroups -- the dispatcher spreads them better)
-  static const int v = [] {
-    const char* e = getenv("AMR_LANE_WPB");
-    const int k = e ? atoi(e) : 4;
-    return k == 1 || k == 2 ? k : 4;
-  }();
-  return v;
-}
 
 // Cache policy of the streamed intermediates (psk_common.h): AMR_LANE_NT=<mask
 // of the kNt* classes>, 0 = the default policy everywhere; unset = the
@@ -1455,7 +964,7 @@ static int lane_wpb() {
 #define AMR_LANE_NT_MASKS 0, AMR_LANE_NT_DEFAULT, kNtAll
 #endif
 static int lane_nt() {
-  static const int v = [] { const char* e = getenv("AMR_LANE_NT"); return e ? atoi(e) : AMR_LANE_NT_DEFAULT; }();
+  static const int v = (int)env_int("AMR_LANE_NT", INT32_MIN, INT32_MAX, AMR_LANE_NT_DEFAULT);
   return v;
 }
 template <typename Fn, int... M>
@@ -1470,26 +979,7 @@ static bool with_lane_nt(Fn&& fn) {
 
 static int lane_dev_fence() {
   // AMR_LANE_FENCE=1: the device-scope fence after a forward pass (lane_pass_fence, psk_common.h)
-  static const int v = [] { const char* e = getenv("AMR_LANE_FENCE"); return e && e[0] == '1' ? 1 : 0; }();
-  return v;
-}
-
-static int bp_split() {
-  // role-split band-pass (k_bp_lane2): AMR_BP_SPLIT=0 turns it off
-  static const int v = [] { const char* e = getenv("AMR_BP_SPLIT"); return e && e[0] == '0' ? 0 : 1; }();
-  return v;
-}
-
-static int bp_prefwd() {
-  // the band-pass forward pass as its own launch (k_bp_fwd) before the
-  // role-split re-run / backward kernel: AMR_BP_PREFWD=1 / 0
-  static const int v = [] { const char* e = getenv("AMR_BP_PREFWD"); return e && e[0] == '1' ? 1 : 0; }();
-  return v;
-}
-
-static int bp_ck() {
-  // band-pass checkpoint every AMR_BP_CK tiles (1 or 2; the LDS hand-off stays one tile)
-  static const int v = [] { const char* e = getenv("AMR_BP_CK"); return e && e[0] == '2' ? 2 : 1; }();
+  static const int v = env_on("AMR_LANE_FENCE");
   return v;
 }
 
@@ -1513,68 +1003,35 @@ static void with_bp_zo(int zo, Fn&& fn) {
 template <typename T>
 static hipError_t launch_bp(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st) {
   const int64_t g = (b.n_streams + 63) / 64;
+  const dim3 grid((unsigned)((g + 1) / 2)), block(256);   // two groups per workgroup
   if (b.f32f) {
-    // the float32 hand-off (the default throughput configuration only: split
-    // roles, 4-wave workgroups, 32-sample checkpoints); its fix-up launch
-    // comes after the low-pass, which flags streams too
-    // (launch_psk_bandpass_fixup)
-    if (!(bp_split() && lane_wpb() >= 2 && !bp_prefwd() && bp_ck() == 1)) return hipErrorInvalidValue;
+    // the float32 hand-off; its fix-up launch comes after the low-pass, which
+    // flags streams too (launch_psk_bandpass_fixup)
     hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
     if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((g + 1) / 2)), block(256);
     with_bp_zo(bp_zero_taps(p), [&](auto z) {
-      hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 1, true>), grid, block, 0, st, b, p, f,
+      hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, true>), grid, block, 0, st, b, p, f,
                          lane_dev_fence());
     });
     return hipGetLastError();
   }
-  if (bp_split()) {
-    const int zo = bp_zero_taps(p);
-    if (zo) {
-      hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
-      if (e != hipSuccess) return e;
-    }
-    const dim3 grid((unsigned)(lane_wpb() >= 2 ? (g + 1) / 2 : g)), block(lane_wpb() >= 2 ? 256 : 128);
-    if (lane_wpb() >= 2 && bp_prefwd()) {
-      const dim3 fgrid((unsigned)((g + 3) / 4));
-      with_bp_zo(zo, [&](auto z) {
-        constexpr int ZO = decltype(z)::value;
-        hipLaunchKernelGGL((k_bp_fwd<T, ZO>), fgrid, dim3(256), 0, st, b, p, f);
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, ZO, false, true>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      });
-    } else if (lane_wpb() >= 2 && bp_ck() == 2) {
-      with_bp_zo(zo, [&](auto z) {
-        hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 2>), grid, block, 0, st, b, p, f,
-                           lane_dev_fence());
-      });
-    } else if (lane_wpb() >= 2) {
-      // the default path: the cache policies of AMR_LANE_NT (its fix-up launch below inherits them)
-      const bool ok = with_lane_nt([&](auto m) {
-        constexpr int NT = decltype(m)::value;
-        with_bp_zo(zo, [&](auto z) {
-          hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, 1, false, NT>), grid, block, 0, st, b, p,
-                             f, lane_dev_fence());
-        });
-        if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
-          hipLaunchKernelGGL((k_bp_lane2<T, 1, 0, true, false, 1, false, NT>), dim3((unsigned)g), dim3(128), 0, st, b,
-                             p, f, lane_dev_fence());
-      });
-      return ok ? hipGetLastError() : hipErrorInvalidValue;
-    } else {
-      with_bp_zo(zo, [&](auto z) {
-        hipLaunchKernelGGL((k_bp_lane2<T, 1, decltype(z)::value>), grid, block, 0, st, b, p, f, lane_dev_fence());
-      });
-    }
+  const int zo = bp_zero_taps(p);
+  if (zo) {
+    hipError_t e = hipMemsetAsync(b.bp_flags, 0, (size_t)b.n_streams * 4, st);
+    if (e != hipSuccess) return e;
+  }
+  // the cache policies of AMR_LANE_NT; the fix-up launch inherits them
+  const bool ok = with_lane_nt([&](auto m) {
+    constexpr int NT = decltype(m)::value;
+    with_bp_zo(zo, [&](auto z) {
+      hipLaunchKernelGGL((k_bp_lane2<T, 2, decltype(z)::value, false, false, NT>), grid, block, 0, st, b, p, f,
+                         lane_dev_fence());
+    });
     if (zo)   // every tap for the groups holding a flagged stream (the others exit at once)
-      hipLaunchKernelGGL((k_bp_lane2<T, 1, 0, true>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
-    return hipGetLastError();
-  }
-  switch (lane_wpb()) {
-    case 4: hipLaunchKernelGGL((k_bp_lane<T, 4>), dim3((unsigned)((g + 3) / 4)), dim3(256), 0, st, b, p, f, lane_dev_fence()); break;
-    case 2: hipLaunchKernelGGL((k_bp_lane<T, 2>), dim3((unsigned)((g + 1) / 2)), dim3(128), 0, st, b, p, f, lane_dev_fence()); break;
-    default: hipLaunchKernelGGL((k_bp_lane<T, 1>), dim3((unsigned)g), dim3(64), 0, st, b, p, f, lane_dev_fence());
-  }
-  return hipGetLastError();
+      hipLaunchKernelGGL((k_bp_lane2<T, 1, 0, true, false, NT>), dim3((unsigned)g), dim3(128), 0, st, b, p, f,
+                         lane_dev_fence());
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_psk_bandpass_lane(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st) {
@@ -1601,97 +1058,84 @@ hipError_t launch_psk_bandpass_fixup(const PskBuffers& b, const PskParams& p, co
   return hipGetLastError();
 }
 
-static int lp_split() {
-  // role-split low-pass (k_lp_lane2): AMR_LP_SPLIT=1 turns it on (off by
-  // default: its 20-sample tiles double the checkpoint traffic and leave its
-  // loads less time; 4.54 vs 4.29 ms/step at 16 in flight, same solo time)
-  static const int v = [] { const char* e = getenv("AMR_LP_SPLIT"); return e && e[0] == '1' ? 1 : 0; }();
-  return v;
-}
-
 static int lp_half() {
   // the fused low-pass with both components in one wave (k_lp_lane_h) in
   // place of the two-wave fused k_lp_lane: AMR_LP_HALF=1 / 0 forces it on /
-  // off; on by default (static symbol slots, 4-wave workgroups, float64 f)
-  static const int v = [] { const char* e = getenv("AMR_LP_HALF"); return e ? (e[0] == '1' ? 1 : 0) : 1; }();
+  // off; on by default (static symbol slots, float64 f)
+  static const int v = env_tri("AMR_LP_HALF") != 0;
   return v;
 }
 
-// which low-pass ran (AMR_LP_* of amr.h), returned by launch_lp
+// Whether a batch's low-pass should slice inside its backward pass, given
+// static symbol slots: once at least 32768 streams are live.  The fused slicer
+// saves the symbols' HBM round trip (+4-5 % per step at 16 x 4096 in flight)
+// but lengthens a lone batch's low-pass (11.0 -> 13.7 ms in the two-wave form,
+// where the re wave slices between barriers; 12.7 ms in k_lp_lane_h: still
+// above 11.0, so the threshold stays), which is what a small live set (a
+// 1024-stream shard) waits on.  AMR_FUSED_SLICE=1 / 0 forces it on / off;
+// PskBuffers::no_fuse (the soft-output calls) always turns it off.
+static bool lp_fuse_wanted(const PskBuffers& b) {
+  static const int fuse_env = env_tri("AMR_FUSED_SLICE");
+  const int64_t live = b.n_streams * (b.inflight > 1 ? b.inflight : 1);
+  return !b.no_fuse && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
+}
+
+// fn(std::integral_constant<int, SPS>, std::integral_constant<int, FM>) for the
+// plan's static symbol slots -- the (sps, first % sps) pairs compiled in, while
+// first <= kLpStaticFirstMax (the C ABI allows any first) -- or fn(0, 0): the
+// generic kernel.  Returns what fn returns.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <typename Fn>
+static int with_lp_slots(const PskParams& p, Fn&& fn) {
+  const int fm = (int)(p.first % (p.sps > 0 ? p.sps : 1));
+  if (p.first <= kLpStaticFirstMax) {
+    if (p.sps == 10 && fm == 5) return fn(Int<10>{}, Int<5>{});
+    if (p.sps == 5 && fm == 2) return fn(Int<5>{}, Int<2>{});
+    if (p.sps == 20 && fm == 10) return fn(Int<20>{}, Int<10>{});
+    if (p.sps == 10 && fm == 0) return fn(Int<10>{}, Int<0>{});
+    if (p.sps == 5 && fm == 0) return fn(Int<5>{}, Int<0>{});
+    if (p.sps == 20 && fm == 0) return fn(Int<20>{}, Int<0>{});
+  }
+  return fn(Int<0>{}, Int<0>{});
+}
+
+// which low-pass ran (AMR_LP_* of amr.h), returned by launch_lp; -1: an
+// AMR_LANE_NT mask that is not compiled in
 template <int S_, int F_>
 static int launch_lp(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st) {
   const int64_t g = (b.n_streams + 63) / 64;
-  if (lp_split()) {
-    hipLaunchKernelGGL((k_lp_lane2<S_, F_, kLpT2>), dim3((unsigned)g), dim3(256), 0, st, b, p, f);
-    return AMR_LP_LANE;
-  }
-  // the slicer inside the low-pass (static slots, both components in one
-  // workgroup) once at least 32768 streams are live: it saves the symbols'
-  // HBM round trip (+4-5 % per step at 16 x 4096 in flight) but lengthens a
-  // lone batch's low-pass (11.0 -> 13.7 ms in the two-wave form, where the
-  // re wave slices between barriers; 12.7 ms in k_lp_lane_h: still above
-  // 11.0, so the threshold stays), which is what a small live set (a
-  // 1024-stream shard) waits on.  AMR_FUSED_SLICE=1 / 0 forces it on / off.
-  static const int fuse_env = [] {
-    const char* e = getenv("AMR_FUSED_SLICE");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  const int64_t live = b.n_streams * (b.inflight > 1 ? b.inflight : 1);
-  const bool fuse = S_ > 0 && lane_wpb() >= 2 && !b.no_fuse && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
+  const dim3 grid((unsigned)((g + 1) / 2)), block(256);   // two groups per workgroup
+  const bool fuse = S_ > 0 && lp_fuse_wanted(b);
   if (b.f32f) {
     // the float32 hand-off needs the fused slicer (api.cpp asks psk_lane_fused first)
-    if (!(fuse && S_ != 0 && lane_wpb() == 4)) return AMR_LP_LANE;
-    hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, S_ != 0>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b, p, f, lane_dev_fence());
+    if (!fuse) return AMR_LP_LANE;
+    hipLaunchKernelGGL((k_lp_lane<S_, F_, S_ != 0, S_ != 0>), grid, block, 0, st, b, p, f, lane_dev_fence());
     return AMR_LP_LANE_FUSED;
   }
   if constexpr (S_ != 0) {
     // (k_lp_lane_h offsets a half's words by a 32-bit lane term: 32 * n_words must fit)
-    if (fuse && lane_wpb() == 4 && lp_half() && p.n_words < (1 << 26)) {
+    if (fuse && lp_half() && p.n_words < (1 << 26)) {
       const bool ok = with_lane_nt([&](auto m) {
-        hipLaunchKernelGGL((k_lp_lane_h<S_, F_, decltype(m)::value>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b,
-                           p, f, lane_dev_fence());
+        hipLaunchKernelGGL((k_lp_lane_h<S_, F_, decltype(m)::value>), grid, block, 0, st, b, p, f, lane_dev_fence());
       });
       return ok ? AMR_LP_LANE_HALF : -1;
     }
   }
-  switch (lane_wpb()) {
-    case 4: {
-      // (under 32768 live streams, the soft-output calls, AMR_LP_HALF=0: the same cache policies)
-      const bool ok = with_lane_nt([&](auto m) {
-        constexpr int NT = decltype(m)::value;
-        if (fuse)
-          hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, S_ != 0, false, NT>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st,
-                             b, p, f, lane_dev_fence());
-        else
-          hipLaunchKernelGGL((k_lp_lane<S_, F_, 4, false, false, NT>), dim3((unsigned)((g + 1) / 2)), dim3(256), 0, st, b,
-                             p, f, lane_dev_fence());
-      });
-      if (!ok) return -1;
-      break;
-    }
-    case 2:
-      if (fuse) hipLaunchKernelGGL((k_lp_lane<S_, F_, 2, S_ != 0>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
-      else hipLaunchKernelGGL((k_lp_lane<S_, F_, 2>), dim3((unsigned)g), dim3(128), 0, st, b, p, f, lane_dev_fence());
-      break;
-    default:
-      // a multiple of 16 blocks: the re/im XCD pairing is a bijection
-      hipLaunchKernelGGL((k_lp_lane<S_, F_, 1>), dim3((unsigned)((2 * g + 15) / 16 * 16)), dim3(64), 0, st, b, p, f, lane_dev_fence());
-  }
+  // (under 32768 live streams, the soft-output calls, AMR_LP_HALF=0: the same cache policies)
+  const bool ok = with_lane_nt([&](auto m) {
+    constexpr int NT = decltype(m)::value;
+    if (fuse) hipLaunchKernelGGL((k_lp_lane<S_, F_, S_ != 0, false, NT>), grid, block, 0, st, b, p, f, lane_dev_fence());
+    else hipLaunchKernelGGL((k_lp_lane<S_, F_, false, false, NT>), grid, block, 0, st, b, p, f, lane_dev_fence());
+  });
+  if (!ok) return -1;
   return fuse ? AMR_LP_LANE_FUSED : AMR_LP_LANE;
 }
 
 // whether launch_psk_lowpass_lane will run the fused slicer for this batch
 // (the float32 hand-off's precondition, api.cpp)
 bool psk_lane_fused(const PskBuffers& b, const PskParams& p) {
-  const int fm = (int)(p.first % (p.sps > 0 ? p.sps : 1));
-  const bool stat = p.first <= kLpT2 && ((p.sps == 10 && (fm == 5 || fm == 0)) || (p.sps == 5 && (fm == 2 || fm == 0)) ||
-                                         (p.sps == 20 && (fm == 10 || fm == 0)));
-  static const int fuse_env = [] {
-    const char* e = getenv("AMR_FUSED_SLICE");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  const int64_t live = b.n_streams * (b.inflight > 1 ? b.inflight : 1);
-  return stat && !lp_split() && lane_wpb() == 4 && !b.no_fuse && (fuse_env >= 0 ? fuse_env == 1 : live >= 32768);
+  return with_lp_slots(p, [](auto s, auto) { return (int)decltype(s)::value; }) > 0 && lp_fuse_wanted(b);
 }
 
 hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, const Iir& f, hipStream_t st,
@@ -1699,19 +1143,9 @@ hipError_t launch_psk_lowpass_lane(const PskBuffers& b, const PskParams& p, cons
   if (f.nt != 5) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(b.flags, 0, (size_t)b.n_streams * 4, st);
   if (e != hipSuccess) return e;
-  const int fm = (int)(p.first % (p.sps > 0 ? p.sps : 1));
-  int fused = AMR_LP_LANE;
-  // the static symbol slots number tile t's symbols from t * (TL / SPS) - first / SPS:
-  // valid (>= 0 from the first whole tile on) while first <= the tile length;
-  // a later first (the C ABI allows any) takes the generic path
-  if (p.first > kLpT2) fused = launch_lp<0, 0>(b, p, f, st);
-  else if (p.sps == 10 && fm == 5) fused = launch_lp<10, 5>(b, p, f, st);
-  else if (p.sps == 5 && fm == 2) fused = launch_lp<5, 2>(b, p, f, st);
-  else if (p.sps == 20 && fm == 10) fused = launch_lp<20, 10>(b, p, f, st);
-  else if (p.sps == 10 && fm == 0) fused = launch_lp<10, 0>(b, p, f, st);
-  else if (p.sps == 5 && fm == 0) fused = launch_lp<5, 0>(b, p, f, st);
-  else if (p.sps == 20 && fm == 0) fused = launch_lp<20, 0>(b, p, f, st);
-  else fused = launch_lp<0, 0>(b, p, f, st);
+  const int fused = with_lp_slots(p, [&](auto s, auto m) {
+    return launch_lp<decltype(s)::value, decltype(m)::value>(b, p, f, st);
+  });
   if (fused < 0) return hipErrorInvalidValue;   // an AMR_LANE_NT mask that is not compiled in
   if (sliced) *sliced = fused != AMR_LP_LANE;
   if (kernel) *kernel = fused;

@@ -211,8 +211,8 @@ int amr_psk_split_design(const double *bp_b, const double *bp_a, int bp_ntaps, c
 double amr_psk_f32_margin(const double *lp_b, const double *lp_a, int lp_ntaps);
 int amr_psk_plan_last_f32f(const amr_psk_plan *plan);
 /* Diagnostic (tests, A/B runs): which low-pass kernel the plan's last call ran
- * in the lane layout -- AMR_LP_LANE: k_lp_lane or the
- * role-split k_lp_lane2, symbols to HBM; AMR_LP_LANE_FUSED: k_lp_lane with the
+ * in the lane layout -- AMR_LP_LANE: k_lp_lane, symbols to
+ * HBM for the slicer kernel; AMR_LP_LANE_FUSED: k_lp_lane with the
  * slicer fused, a component per wave; AMR_LP_LANE_HALF: k_lp_lane_h, both
  * components in one wave, the slicer inline -- or -1 when that call ran no
  * lane low-pass (another layout, or every stream through the exact path). */
