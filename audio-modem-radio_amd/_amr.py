@@ -68,6 +68,8 @@ EXPORTS = [
     "amr_viterbi_decode_host",
     "amr_psk_demod_soft_host", "amr_psk_demod_soft_device", "amr_psk_soft_host", "amr_viterbi_soft_work_bytes",
     "amr_viterbi_decode_soft_device", "amr_viterbi_decode_soft_host",
+    "amr_rs_encoded_len", "amr_rs_decoded_len", "amr_rs_encode_host", "amr_rs_encode_device", "amr_rs_decode_host",
+    "amr_rs_decode_device",
 ]
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL = 0, 1, 2, 3
@@ -422,6 +424,12 @@ def lib():
             "amr_viterbi_soft_work_bytes": (I64, [I64, I64]),
             "amr_viterbi_decode_soft_device": (I32, [P, P, I64, I64, P, I64, P, I64, P, P, P, I64]),
             "amr_viterbi_decode_soft_host": (I32, [P, I64, I64, P, I64, P, I64, P, P]),
+            "amr_rs_encoded_len": (I64, [I64, I32]),
+            "amr_rs_decoded_len": (I64, [I64, I32]),
+            "amr_rs_encode_host": (I32, [P, I64, P, I64, I32, I32, P, I64, P]),
+            "amr_rs_encode_device": (I32, [P, P, I64, P, I64, I32, I32, P, I64, P]),
+            "amr_rs_decode_host": (I32, [P, I64, P, P, I64, I32, I32, P, I64, P, P, P]),
+            "amr_rs_decode_device": (I32, [P, P, I64, P, P, I64, I32, I32, P, I64, P, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -993,6 +1001,86 @@ def viterbi_decode_soft(softs):
     check(lib().amr_set_device(default_device()))
     check(lib().amr_viterbi_decode_soft_host(ptr(buf), stride, 0, ptr(ln), n, ptr(out), cap, ptr(out_len), ptr(metric)))
     return [out[i, :out_len[i]].tobytes() for i in range(n)], [int(v) for v in metric]
+
+
+RS_MIN_NSYM, RS_MAX_NSYM, RS_MAX_INTERLEAVE = 2, 64, 64
+
+
+def rs_check_code(nsym, interleave):
+    """The Reed-Solomon code's two parameters as ints, or ValueError."""
+    nsym, interleave = int(nsym), int(interleave)
+    if not RS_MIN_NSYM <= nsym <= RS_MAX_NSYM:
+        raise ValueError(f"nsym {nsym} outside [{RS_MIN_NSYM}, {RS_MAX_NSYM}]")
+    if not 1 <= interleave <= RS_MAX_INTERLEAVE:
+        raise ValueError(f"interleave {interleave} outside [1, {RS_MAX_INTERLEAVE}]")
+    return nsym, interleave
+
+
+def rs_encoded_len(n: int, nsym: int) -> int:
+    """n message bytes as ceil(n / (255 - nsym)) blocks with nsym parity bytes each."""
+    return n + -(-n // (255 - nsym)) * nsym
+
+
+def rs_decoded_len(n: int, nsym: int) -> int:
+    """The message bytes of a received length, or -1 when it is not valid: 0, or
+    a last block (what is left after the full blocks of 255) of at least nsym + 1."""
+    if n <= 0:
+        return 0 if n == 0 else -1
+    nblk = -(-n // 255)
+    return n - nblk * nsym if n - 255 * (nblk - 1) >= nsym + 1 else -1
+
+
+def rs_encode(datas, nsym=32, interleave=1):
+    """Batched fec.ReedSolomonCodec.encode on the GPU (amr_rs_encode_host): list[bytes]."""
+    nsym, interleave = rs_check_code(nsym, interleave)
+    require_gpu()
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    if n == 0:
+        return []
+    buf, ln, stride = _pad_rows(datas)
+    cap = max(1, rs_encoded_len(int(ln.max()), nsym))
+    out = np.zeros((n, cap), np.uint8)
+    out_len = np.zeros(n, np.int64)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_rs_encode_host(ptr(buf), stride, ptr(ln), n, nsym, interleave, ptr(out), cap, ptr(out_len)))
+    return [out[i, :out_len[i]].tobytes() for i in range(n)]
+
+
+def rs_decode(datas, nsym=32, interleave=1, erasures=None):
+    """Batched errors-and-erasures decode on the GPU (amr_rs_decode_host).
+    erasures: None, or per row None / the erased stream positions.  Returns
+    (list[bytes], corrected list[int], failed list[int]); a failed block's
+    message bytes are the received ones."""
+    nsym, interleave = rs_check_code(nsym, interleave)
+    require_gpu()
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    if n == 0:
+        return [], [], []
+    buf, ln, stride = _pad_rows(datas)
+    mask = None
+    if erasures is not None:
+        if len(erasures) != n:
+            raise ValueError(f"erasures: {len(erasures)} rows for {n} messages")
+        mask = np.zeros((n, stride), np.uint8)
+        for i, e in enumerate(erasures):
+            if e is None:
+                continue
+            pos = np.asarray(list(e), np.int64).reshape(-1)
+            if pos.size and (pos.min() < 0 or pos.max() >= ln[i]):
+                raise ValueError(f"row {i}: erased position outside [0, {int(ln[i])})")
+            mask[i, pos] = 1
+    cap = max(1, stride)
+    out = np.zeros((n, cap), np.uint8)
+    out_len = np.zeros(n, np.int64)
+    corrected = np.zeros(n, np.int32)
+    failed = np.zeros(n, np.int32)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_rs_decode_host(ptr(buf), stride, ptr(ln), ptr(mask) if mask is not None else None, n, nsym,
+                                   interleave, ptr(out), cap, ptr(out_len), ptr(corrected), ptr(failed)))
+    return ([out[i, :out_len[i]].tobytes() for i in range(n)], [int(v) for v in corrected],
+            [int(v) for v in failed])
 
 
 def psk_soft(kind: str, sym: np.ndarray) -> np.ndarray:

@@ -18,6 +18,15 @@ them, with no reference counterpart:
                                         -> k_viterbi_soft: the same decoder on
                                            int8 soft decisions, as
                                            modem.qpsk_demodulate_soft gives them
+And beside ReedSolomonFEC, which stays the reference's parity stub, the code its
+name promises:
+  ReedSolomonCodec.encode / encode_batch -> k_rs_encode (rs_kernels.hip)
+  ReedSolomonCodec.decode / decode_batch -> k_rs_decode: systematic
+                                           RS(255, 255 - nsym) over GF(2^8)
+                                           (0x11D, alpha = 2, first root alpha^0),
+                                           shortened last block, block interleave,
+                                           errors-and-erasures decoding, one
+                                           wavefront per block
 """
 from __future__ import annotations
 
@@ -63,6 +72,64 @@ class ReedSolomonFEC:
                 if len(d) >= 4 and not ok:
                     print("Aviso: CRC não corresponde - dados podem estar corrompidos")
         return outs, oks
+
+
+class ReedSolomonError(ValueError):
+    """ReedSolomonCodec.decode: a block could not be decoded, or the length is not one of the code."""
+
+
+class ReedSolomonCodec:
+    """Reed-Solomon over GF(2^8) on the GPU (no reference counterpart):
+    field polynomial 0x11D, alpha = 2, generator prod (x - alpha^i), i < nsym.
+    A message is cut into blocks of 255 - nsym bytes (the last one shorter), each
+    followed by nsym parity bytes; a block corrects e errors and f erasures while
+    2 e + f <= nsym.  interleave = I > 1 sends groups of I blocks column by
+    column, so that a burst of I * (nsym // 2) bytes is still corrected."""
+
+    def __init__(self, nsym=32, interleave=1):
+        self.nsym, self.interleave = _amr.rs_check_code(nsym, interleave)
+
+    def encoded_len(self, n: int) -> int:
+        return _amr.rs_encoded_len(n, self.nsym)
+
+    def decoded_len(self, n: int) -> int:
+        """The message bytes of n received bytes, or -1 when n is not a length of this code."""
+        return _amr.rs_decoded_len(n, self.nsym)
+
+    def encode(self, data: bytes) -> bytes:
+        return self.encode_batch([data])[0]
+
+    def encode_batch(self, datas):
+        """encode() of every element, in one launch: list[bytes]."""
+        return _amr.rs_encode(datas, self.nsym, self.interleave)
+
+    def decode(self, data: bytes, erase_pos=None) -> bytes:
+        """The message of a received stream; erase_pos: stream positions known to be
+        unreliable.  ReedSolomonError when a block fails or the length is not valid."""
+        try:
+            outs, _, failed = self.decode_batch([data], None if erase_pos is None else [erase_pos],
+                                                return_status=True)
+        except ValueError as e:
+            if isinstance(e, ReedSolomonError):
+                raise
+            raise ReedSolomonError(str(e)) from None
+        if failed[0]:
+            raise ReedSolomonError(f"{failed[0]} block(s) could not be decoded")
+        return outs[0]
+
+    def decode_batch(self, datas, erasures=None, return_status: bool = False):
+        """decode of every element in one launch: list[bytes]; with
+        return_status=True also (corrected, failed): per message the bytes the
+        decoded blocks changed and the blocks that failed (their message bytes
+        are the received ones).  erasures: None, or per message None / the
+        erased stream positions."""
+        datas = [bytes(d) for d in datas]
+        for i, d in enumerate(datas):
+            if _amr.rs_decoded_len(len(d), self.nsym) < 0:
+                raise ValueError(f"row {i}: {len(d)} bytes is not a length of this code (0, or a last block "
+                                 f"of at least {self.nsym + 1} bytes after the full blocks of 255)")
+        outs, corrected, failed = _amr.rs_decode(datas, self.nsym, self.interleave, erasures)
+        return (outs, corrected, failed) if return_status else outs
 
 
 class ConvolutionalEncoder:

@@ -46,6 +46,9 @@
  *   amr_viterbi_decode_host the maximum-likelihood decoder of that code, batched
  *                           (no reference counterpart: fec.ViterbiDecoder.decode,
  *                           fec.py:126-155, is a stub and stays one in fec.py)
+ *   amr_rs_encode_host      fec.ReedSolomonCodec: systematic RS(255, 255 - nsym) over
+ *   amr_rs_decode_host      GF(2^8), errors-and-erasures decoding, block interleave
+ *                           (no reference counterpart: fec.ReedSolomonFEC is parity)
  *   amr_allgather           the gather of decoded bytes across GPUs (RCCL)
  *
  * Status: every function returns AMR_OK (0) or a negative AMR_E_* code;
@@ -86,7 +89,9 @@ extern "C" {
                                   _device, amr_hell_glyph_rows, AMR_HELL_ELEM_*) and AMR_TX_HELL; the
                                   convolutional code (amr_conv_encoded_len, amr_conv_encode_host,
                                   amr_viterbi_work_bytes, amr_viterbi_decode_host / _device);
-                                  amr_psk_plan_last_lowpass (AMR_LP_*); amr_sync_pack_host (diagnostic) */
+                                  amr_psk_plan_last_lowpass (AMR_LP_*); amr_sync_pack_host (diagnostic);
+                                  the Reed-Solomon code (amr_rs_encoded_len, amr_rs_decoded_len,
+                                  amr_rs_encode_host / _device, amr_rs_decode_host / _device) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -712,6 +717,45 @@ int amr_viterbi_decode_soft_device(amr_psk_plan *plan, const int8_t *d_in, int64
 /* host pointers; a bad length is AMR_E_INVALID (the message names the row) before any device work */
 int amr_viterbi_decode_soft_host(const int8_t *in, int64_t in_stride, int64_t in_offset, const int64_t *in_len,
                                  int64_t n, uint8_t *out, int64_t out_stride, int64_t *out_len, int32_t *metric);
+
+/* ---- Reed-Solomon over GF(2^8) (fec.ReedSolomonCodec) -----------
+ * No reference counterpart: the reference's "Reed-Solomon" is the parity stub amr_fec_decode_host
+ * reproduces.  Field polynomial 0x11D, alpha = 2, generator prod_{i < nsym} (x - alpha^i), 2 <= nsym <= 64,
+ * k = 255 - nsym.  Systematic: a message of n bytes is ceil(n / k) blocks of k bytes (the last 1 .. k), each
+ * followed by its nsym parity bytes -- the remainder of m(x) x^nsym by g, the block's first byte the highest
+ * power; short blocks are shortened codewords.  A received length L is valid when L == 0 or the last block,
+ * L - 255 (ceil(L / 255) - 1) bytes, holds at least nsym + 1.  interleave (1 .. 64; 1: none): consecutive
+ * blocks form groups of `interleave` (the last group may have fewer), and a group's bytes are sent column
+ * by column -- byte c of every block of the group that has a byte c, for c = 0, 1, ...
+ * Decoding: a block with f erased positions decodes to the codeword that differs from it in e positions
+ * outside the erased set with 2 e + f <= nsym (it is unique; received values at erased positions are
+ * ignored); where there is none the block FAILS and its message bytes pass through as received.
+ * corrected[i] = the byte positions of row i's decoded blocks where the codeword differs from the received
+ * block, failed[i] = its failed blocks.  Only out_len[i] bytes of an output row are written. */
+/* n + ceil(n / (255 - nsym)) nsym, or < 0 for a bad argument */
+int64_t amr_rs_encoded_len(int64_t n, int nsym);
+/* the message bytes of a received length L, or -1 when L is not valid (or nsym is out of range) */
+int64_t amr_rs_decoded_len(int64_t L, int nsym);
+/* device pointers, enqueued on the plan's stream (plan may be NULL: the null stream).  The lengths are read
+ * on the device: a row whose length is outside [0, in_stride] gets out_len -1 and nothing else of it is
+ * touched.  out_stride >= amr_rs_encoded_len(in_stride, nsym). */
+int amr_rs_encode_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_stride, const int64_t *d_in_len,
+                         int64_t n, int nsym, int interleave, uint8_t *d_out, int64_t out_stride,
+                         int64_t *d_out_len);
+/* host pointers; a length outside [0, in_stride] is AMR_E_INVALID (the message names the row) */
+int amr_rs_encode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, int64_t n, int nsym,
+                       int interleave, uint8_t *out, int64_t out_stride, int64_t *out_len);
+/* device pointers, on the plan's stream (plan may be NULL).  d_erase is NULL or [n][in_stride] bytes in the
+ * layout of d_in, nonzero = erased.  A row whose length is not valid, or exceeds in_stride, gets out_len 0,
+ * corrected 0 and failed -1 and nothing else of it is touched.  out_stride >= the message bytes of the
+ * longest valid length <= in_stride. */
+int amr_rs_decode_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_stride, const int64_t *d_in_len,
+                         const uint8_t *d_erase, int64_t n, int nsym, int interleave, uint8_t *d_out,
+                         int64_t out_stride, int64_t *d_out_len, int32_t *d_corrected, int32_t *d_failed);
+/* host pointers; a length that is not valid is AMR_E_INVALID (the message names the row) before any device work */
+int amr_rs_decode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, const uint8_t *erase, int64_t n,
+                       int nsym, int interleave, uint8_t *out, int64_t out_stride, int64_t *out_len,
+                       int32_t *corrected, int32_t *failed);
 
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
