@@ -24,7 +24,11 @@ AMR_OK = 0
 AMR_E_INVALID, AMR_E_PADLEN, AMR_E_HIP, AMR_E_NOMEM, AMR_E_NODEVICE, AMR_E_RCCL, AMR_E_CAPACITY = \
     -1, -2, -3, -4, -5, -6, -7
 DTYPE_F32, DTYPE_F64, DTYPE_I16 = 0, 1, 2
-PSK_QPSK, PSK_BPSK = 0, 1
+PSK_QPSK, PSK_BPSK, PSK_D8PSK = 0, 1, 2
+# a demodulator's kind name -> AMR_PSK_* and its bits per symbol; "d8psk" (the
+# 8-ary differential modem) has QPSK's design (design_psk)
+PSK_KINDS = {"qpsk": PSK_QPSK, "bpsk": PSK_BPSK, "d8psk": PSK_D8PSK}
+PSK_BITS = {"qpsk": 2, "bpsk": 1, "d8psk": 3}
 T_NAMES = ["bandpass", "lowpass_fwd", "lowpass_bwd", "lowpass_exact", "sync_pack", "fec", "launch"]
 TF_NAMES = ["bandpass", "hilbert", "decide", "launch", "exact"]
 # amr_frame_rec (include/amr.h), 64 bytes
@@ -72,8 +76,8 @@ EXPORTS = [
     "amr_rs_decode_device",
 ]
 
-TX_BPSK, TX_QPSK, TX_FSK, TX_HELL = 0, 1, 2, 3
-TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL}
+TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK = 0, 1, 2, 3, 4
+TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL, "d8psk": TX_D8PSK}
 
 # AMR_HELL_ELEM_* (include/amr.h): the element types the Hellschreiber receiver reads
 HELL_PCM16 = 11
@@ -194,14 +198,15 @@ def modulate(mode: int, datas, baud, f0, f1=0.0, samp_rate=96000, n_out=None, pc
 
 def psk_slice(kind: str, sym: np.ndarray) -> np.ndarray:
     """The slicer stage alone on the GPU (K4a): sym [B][S] complex128 -> the
-    decided bits [B][bits] as uint8 (modem.py:214-241 QPSK, :100-105 BPSK)."""
+    decided bits [B][bits] as uint8 (modem.py:214-241 QPSK, :100-105 BPSK;
+    "d8psk": k_slice8's eight sectors, 3 bits per product)."""
     require_gpu()
     sym = np.ascontiguousarray(np.atleast_2d(sym), np.complex128)
     B, S = sym.shape
-    nbits = max(0, (S - 1) * (2 if kind == "qpsk" else 1))
+    nbits = max(0, (S - 1) * PSK_BITS[kind])
     nw = max(1, (nbits + 31) // 32)
     words = np.zeros((B, nw), np.uint32)
-    check(lib().amr_psk_slice_host(PSK_QPSK if kind == "qpsk" else PSK_BPSK, ptr(sym), B, S, ptr(words)))
+    check(lib().amr_psk_slice_host(PSK_KINDS[kind], ptr(sym), B, S, ptr(words)))
     bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
     return bits[:, :nbits]
 
@@ -503,9 +508,10 @@ def design_psk(kind: str, n: int, baud, carrier=3000.0, samp_rate=96000):
     Order of the reference's failure points is kept: band-pass design,
     band-pass filtfilt padlen check, low-pass design (modem.py:76-88 / 197-204)."""
     from scipy import signal
+    PSK_KINDS[kind]                                      # KeyError names an unknown kind
     sps = int(samp_rate / baud)
     nyq = samp_rate / 2
-    if kind == "qpsk":
+    if kind in ("qpsk", "d8psk"):
         low = (carrier - baud * 1.5) / nyq
         high = (carrier + baud * 1.5) / nyq
         first = sps // 2
@@ -619,7 +625,7 @@ class PskPlan:
         h = ctypes.c_void_p()
         b, a, zi = self.bp
         bl, al, zil = self.lp
-        check(lib().amr_psk_plan_create(ctypes.byref(h), self.device, PSK_QPSK if kind == "qpsk" else PSK_BPSK,
+        check(lib().amr_psk_plan_create(ctypes.byref(h), self.device, PSK_KINDS[kind],
                                         n, self.sps, self.first, ptr(b), ptr(a), ptr(zi), len(b),
                                         ptr(bl), ptr(al), ptr(zil), len(bl), ptr(lo4), self.max_streams))
         self.handle = h
@@ -887,11 +893,10 @@ def get_psk_plan(kind: str, n: int, baud, carrier, samp_rate, batch: int) -> Psk
     key = ("psk", kind, int(n), float(baud), float(carrier), float(samp_rate), dev)
     need = stream_bucket(batch, PSK_MAX_CHUNK)
     sps = int(samp_rate / baud)
-    first = sps // 2 if kind == "qpsk" else sps
+    first = sps if kind == "bpsk" else sps // 2
 
     def estimate(m):
-        return max(0, int(lib().amr_psk_plan_bytes_estimate(PSK_QPSK if kind == "qpsk" else PSK_BPSK, int(n), sps,
-                                                            first, 9, 5, m)))
+        return max(0, int(lib().amr_psk_plan_bytes_estimate(PSK_KINDS[kind], int(n), sps, first, 9, 5, m)))
     return plan_cache.get(key, need, lambda m: PskPlan(kind, n, baud, carrier, samp_rate, max_streams=m, device=dev),
                           estimate if sps >= 1 else None)
 
@@ -1089,9 +1094,9 @@ def psk_soft(kind: str, sym: np.ndarray) -> np.ndarray:
     require_gpu()
     sym = np.ascontiguousarray(np.atleast_2d(sym), np.complex128)
     B, S = sym.shape
-    nbits = max(0, (S - 1) * (2 if kind == "qpsk" else 1))
+    nbits = max(0, (S - 1) * PSK_BITS[kind])
     soft = np.zeros((B, nbits), np.int8)
-    check(lib().amr_psk_soft_host(PSK_QPSK if kind == "qpsk" else PSK_BPSK, ptr(sym), B, S, ptr(soft)))
+    check(lib().amr_psk_soft_host(PSK_KINDS[kind], ptr(sym), B, S, ptr(soft)))
     return soft
 
 

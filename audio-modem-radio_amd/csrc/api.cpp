@@ -28,6 +28,8 @@ hipError_t launch_psk_lowpass_bwd(const PskBuffers&, const PskParams&, const Iir
 hipError_t launch_psk_lowpass_exact(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_slice(const PskBuffers&, const PskParams&, hipStream_t, bool only_flagged = false);
 hipError_t launch_psk_soft(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
+hipError_t launch_psk_slice8(const PskBuffers&, const PskParams&, hipStream_t, bool only_flagged = false);
+hipError_t launch_psk_soft8(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
 hipError_t launch_psk_bandpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_bandpass_fixup(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 bool psk_lane_fused(const PskBuffers&, const PskParams&);
@@ -293,6 +295,16 @@ struct LastCall {
   }
 };
 
+bool psk_kind_ok(int kind) { return kind == AMR_PSK_QPSK || kind == AMR_PSK_BPSK || kind == AMR_PSK_D8PSK; }
+int psk_bits_per_symbol(int kind) { return kind == AMR_PSK_D8PSK ? 3 : kind == AMR_PSK_QPSK ? 2 : 1; }
+// the slicer and the soft stage of the plan's kind (K4a / K4s, or d8psk's psk8_kernels.hip)
+hipError_t psk_slice_kind(const PskBuffers& b, const PskParams& p, hipStream_t st, bool only_flagged = false) {
+  return p.kind == kD8psk ? launch_psk_slice8(b, p, st, only_flagged) : launch_psk_slice(b, p, st, only_flagged);
+}
+hipError_t psk_soft_kind(const PskBuffers& b, const PskParams& p, int8_t* soft, int64_t stride, hipStream_t st) {
+  return p.kind == kD8psk ? launch_psk_soft8(b, p, soft, stride, st) : launch_psk_soft(b, p, soft, stride, st);
+}
+
 // bytes of s1 / s3 each layout needs (psk_kernels.hip / psk_lane_kernels.hip)
 int64_t lane_s1_bytes(const amr_psk_plan* pl) {
   const int64_t g = pl->groups;
@@ -324,8 +336,7 @@ void psk_geometry(amr_psk_plan* pl, int kind, int64_t n, int64_t sps, int64_t fi
   p.first = first;
   p.kind = kind;
   p.n_sym = n > first ? (n - first + sps - 1) / sps : 0;
-  const int bps = kind == AMR_PSK_QPSK ? 2 : 1;
-  p.n_bits = p.n_sym >= 2 ? (p.n_sym - 1) * bps : 0;
+  p.n_bits = p.n_sym >= 2 ? (p.n_sym - 1) * psk_bits_per_symbol(kind) : 0;
   p.n_words = p.n_bits > 0 ? (p.n_bits + 31) / 32 : 1;
   pl->max_streams = max_streams;
   pl->groups = (max_streams + kWave - 1) / kWave;
@@ -509,7 +520,7 @@ int amr_psk_plan_create(amr_psk_plan** out, int device, int kind, int64_t n, int
   if (!out || !bp_b || !bp_a || !bp_zi || !lp_b || !lp_a || !lp_zi || !lo4)
     return fail(AMR_E_INVALID, "amr_psk_plan_create: NULL argument");
   *out = nullptr;
-  if (kind != AMR_PSK_QPSK && kind != AMR_PSK_BPSK) return fail(AMR_E_INVALID, "unknown PSK kind");
+  if (!psk_kind_ok(kind)) return fail(AMR_E_INVALID, "unknown PSK kind");
   if (sps < 1 || first < 0 || max_streams < 1) return fail(AMR_E_INVALID, "bad sps/first/max_streams");
   if (bp_nt != 9 && bp_nt != 7) return fail(AMR_E_INVALID, "band-pass must have 7 or 9 taps");
   if (lp_nt != 5) return fail(AMR_E_INVALID, "low-pass must have 5 taps");
@@ -603,7 +614,7 @@ int64_t amr_psk_plan_scratch_bytes(const amr_psk_plan* plan) {
 
 int64_t amr_psk_plan_bytes_estimate(int kind, int64_t n, int64_t sps, int64_t first, int bp_nt, int lp_nt,
                                     int64_t max_streams) {
-  if ((kind != AMR_PSK_QPSK && kind != AMR_PSK_BPSK) || n < 1 || sps < 1 || first < 0 || max_streams < 1 ||
+  if (!psk_kind_ok(kind) || n < 1 || sps < 1 || first < 0 || max_streams < 1 ||
       bp_nt < 1 || lp_nt < 1)
     return fail(AMR_E_INVALID, "amr_psk_plan_bytes_estimate: bad argument");
   amr_psk_plan pl;
@@ -700,7 +711,8 @@ int amr_psk_split_bounds_host(amr_psk_plan* plan, const void* x, int dtype, int6
   if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
   if (dtype_size(dtype) == 0 || x_stride < plan->p.n) return fail(AMR_E_INVALID, "bad dtype / x_stride");
   if (!plan->split_designed) split_design(plan);
-  if (!plan->split_ok || plan->p.n_sym < 2) return fail(AMR_E_INVALID, "no time-split layout for this plan");
+  if (!plan->split_ok || plan->p.n_sym < 2 || plan->p.kind == kD8psk)
+    return fail(AMR_E_INVALID, "no time-split layout for this plan");
   // KS5 launches no strict kernel without decision bits: nothing to copy back
   if (plan->p.n_bits < 1 || plan->p.n_words < 1)
     return fail(AMR_E_INVALID, "amr_psk_split_bounds_host: this plan has no decision bits");
@@ -1060,7 +1072,8 @@ int pick_layout(amr_psk_plan* pl, int64_t B, bool soft) {
   // the lane kernels are written for butter(4) band-pass / low-pass
   // coefficient shapes: 9 taps and a palindromic 5-tap low-pass
   if (layout == AMR_LAYOUT_LANE && !(pl->bp.nt == 9 && pl->p.lp_sym)) layout = AMR_LAYOUT_ROW;
-  if (layout == AMR_LAYOUT_SPLIT && soft) layout = AMR_LAYOUT_ROW;
+  // (a d8psk plan likewise: its eight decision boundaries have no margin test yet)
+  if (layout == AMR_LAYOUT_SPLIT && (soft || pl->p.kind == kD8psk)) layout = AMR_LAYOUT_ROW;
   if (layout == AMR_LAYOUT_SPLIT) {
     if (!pl->split_designed) split_design(pl);
     if (!pl->split_ok || B > 65535 || pl->p.n_sym < 2) layout = AMR_LAYOUT_ROW;
@@ -1089,7 +1102,7 @@ PskBuffers psk_buffers(amr_psk_plan* pl, const PskCall& c) {
   b.out_len = c.io.len;
   b.sync_idx = c.io.sync;
   b.edge = c.edge;
-  b.no_fuse = c.soft.ptr ? 1 : 0;
+  b.no_fuse = c.soft.ptr || pl->p.kind == kD8psk ? 1 : 0;   // (the fused slicers decide QPSK / BPSK only)
   return b;
 }
 
@@ -1127,10 +1140,10 @@ int run_psk_row(amr_psk_plan* pl, const PskCall& c, PskBuffers b, bool gated = f
   }
   HIP_TRY_TIMED(*pl, slot(AMR_T_LOWPASS_EXACT), launch_psk_lowpass_exact(b, pl->p, pl->lp, st));
   return timed(*pl, slot(AMR_T_SYNC_PACK), [&]() -> int {
-    HIP_TRY(launch_psk_slice(b, pl->p, st));
+    HIP_TRY(psk_slice_kind(b, pl->p, st));
     if (!gated) HIP_TRY(gate_wait(pl->gate, st));      // the outputs: after any gather still reading them
     HIP_TRY(psk_sync_pack(pl, c.io, b.words, b.gate));
-    if (c.soft.ptr) HIP_TRY(launch_psk_soft(b, pl->p, c.soft.ptr, c.soft.stride, st));
+    if (c.soft.ptr) HIP_TRY(psk_soft_kind(b, pl->p, c.soft.ptr, c.soft.stride, st));
     return AMR_OK;
   });
 }
@@ -1164,10 +1177,10 @@ int run_psk_lane(amr_psk_plan* pl, const PskCall& c, PskBuffers b) {
       }))
     return rc;
   return timed(*pl, AMR_T_SYNC_PACK, [&]() -> int {
-    HIP_TRY(launch_psk_slice(b, pl->p, st, sliced));   // then only the K3x streams
+    HIP_TRY(psk_slice_kind(b, pl->p, st, sliced));     // then only the K3x streams
     HIP_TRY(gate_wait(pl->gate, st));                  // the outputs: after any gather still reading them
     HIP_TRY(psk_sync_pack(pl, c.io, b.words));
-    if (c.soft.ptr) HIP_TRY(launch_psk_soft(b, pl->p, c.soft.ptr, c.soft.stride, st));
+    if (c.soft.ptr) HIP_TRY(psk_soft_kind(b, pl->p, c.soft.ptr, c.soft.stride, st));
     return AMR_OK;
   });
 }
@@ -1479,13 +1492,13 @@ int amr_synth_tile_noise(const float* d_base, int64_t n_base, int64_t n_samples,
 static int psk_symbol_stages(const char* who, int kind, const double* sym, int64_t n_streams, int64_t n_sym,
                              uint32_t* words, int8_t* soft) {
   const std::string name(who);
-  if (kind != AMR_PSK_QPSK && kind != AMR_PSK_BPSK) return fail(AMR_E_INVALID, name + ": unknown PSK kind");
+  if (!psk_kind_ok(kind)) return fail(AMR_E_INVALID, name + ": unknown PSK kind");
   if (n_streams < 0 || n_sym < 0 || (n_streams && n_sym && (!sym || (!words && !soft))))
     return fail(AMR_E_INVALID, name + ": bad argument");
   PskParams p{};
   p.kind = kind;
   p.n_sym = n_sym;
-  p.n_bits = n_sym >= 2 ? (n_sym - 1) * (kind == AMR_PSK_QPSK ? 2 : 1) : 0;
+  p.n_bits = n_sym >= 2 ? (n_sym - 1) * psk_bits_per_symbol(kind) : 0;
   p.n_words = p.n_bits > 0 ? (p.n_bits + 31) / 32 : 1;
   if (n_streams == 0 || p.n_bits == 0) return AMR_OK;
   // the symbol buffer layout the low-pass kernels write: [B/64][re, im][S][64] (psk_common.h sym_index)
@@ -1505,8 +1518,8 @@ static int psk_symbol_stages(const char* who, int kind, const double* sym, int64
   b.n_streams = n_streams;
   b.s1 = d_sym.as<double>();
   b.words = d_words.as<uint32_t>();
-  HIP_TRY_ELSE(launch_psk_slice(b, p, nullptr), bad);
-  if (soft) HIP_TRY_ELSE(launch_psk_soft(b, p, d_soft.as<int8_t>(), p.n_bits, nullptr), bad);
+  HIP_TRY_ELSE(psk_slice_kind(b, p, nullptr), bad);
+  if (soft) HIP_TRY_ELSE(psk_soft_kind(b, p, d_soft.as<int8_t>(), p.n_bits, nullptr), bad);
   HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
   if (words)
     HIP_TRY_ELSE(hipMemcpy(words, d_words.get(), (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost), bad);

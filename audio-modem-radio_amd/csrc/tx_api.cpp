@@ -36,13 +36,15 @@ int64_t tx_symbols(int mode, int64_t nb) {
   if (mode == AMR_TX_QPSK) return 40 + 4 * nb;
   if (mode == AMR_TX_BPSK) return 80 + 8 * nb;
   if (mode == AMR_TX_HELL) return 105 + 51 * nb;             // pixels: 70 + 51 per character + 35
+  if (mode == AMR_TX_D8PSK) return 40 + (8 * nb + 2) / 3;    // ([0,0,0]*30 + [1,1,0]*10 + 8n bits, zero-padded) / 3
   return 8 * (4 + nb);
 }
 
 // samples per symbol as the reference computes it; an AMR_E_* code (< 0 with
 // the message set) when the reference raises for these parameters
 int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_out, TxParams* p) {
-  if (mode != AMR_TX_BPSK && mode != AMR_TX_QPSK && mode != AMR_TX_FSK && mode != AMR_TX_HELL)
+  if (mode != AMR_TX_BPSK && mode != AMR_TX_QPSK && mode != AMR_TX_FSK && mode != AMR_TX_HELL &&
+      mode != AMR_TX_D8PSK)
     return fail(AMR_E_INVALID, "unknown modulation mode");
   if (baud == 0.0) return fail(AMR_E_INVALID, "float division by zero");
   if (!std::isfinite(baud) || !std::isfinite(fs)) return fail(AMR_E_INVALID, "baud and sample_rate must be finite");
@@ -73,7 +75,9 @@ int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_o
     p->ramp = (int64_t)((double)p->sps * 0.1);               // int(len(symbol) * 0.1)
     p->c0 = 2.0 * kPi * f0;
     p->c1 = p->c0;
-    if (p->sps > 0 && p->ramp == 0)                          // envelope[-0:] = linspace(1, 0, 0)
+    // d8psk (no reference counterpart): an empty ramp is an envelope of ones, no symbol is an error
+    if (mode == AMR_TX_D8PSK && p->sps < 1) return fail(AMR_E_INVALID, "d8psk: fewer than one sample per symbol");
+    if (mode != AMR_TX_D8PSK && p->sps > 0 && p->ramp == 0)  // envelope[-0:] = linspace(1, 0, 0)
       return fail(AMR_E_INVALID, "could not broadcast input array from shape (0,) into shape (" +
                                      std::to_string(p->sps) + ",)");
   }

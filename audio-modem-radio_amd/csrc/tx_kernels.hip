@@ -6,6 +6,7 @@
 //   fsk_modulate    /root/reference/modem.py:270-295  CPFSK, phase mod 2*pi
 //   wav_from_array  /root/reference/modem.py:360-368  int16(arr * 32767)
 //   hellschreiber_modulate  hellschreiber.py:109-152  (AMR_TX_HELL, below)
+//   d8psk_modulate  no reference counterpart          (AMR_TX_D8PSK, below)
 //
 // Three launches per call:
 //   T0 k_tx_tables  the per-symbol tables the reference rebuilds per symbol:
@@ -242,6 +243,133 @@ __global__ __launch_bounds__(256) void k_tx_synth(const uint8_t* __restrict__ da
   }
 }
 
+// ---- AMR_TX_D8PSK: d8psk_modulate (amr.h) ----
+// The bits [0,0,0]*30 + [1,1,0]*10 + payload, zero-padded to a multiple of 3;
+// three at a time (MSB first) they are g = 4 b2 + 2 b1 + b0, the Gray code of
+// the phase-step index m (g = m ^ (m >> 1), so m = g ^ (g >> 1) ^ (g >> 2)),
+// and the step is float(k) * (pi / 4), k = m for m <= 4, m - 8 above: every
+// product exact (a power-of-2 scaling of pi), the sum ph = ph + step the one
+// rounding per symbol, sequential from 0.0.
+//   T1 k_tx_phase8  T1's pattern, lane per stream: the preamble's 40 symbols
+//                   (30 steps of 0, 10 of pi), then the payload 3 bytes = 8
+//                   symbols at a time, the tail's missing bytes read as zero.
+//   T2 k_tx_synth8  sin(((2 pi) f0) * (n / fs) + phase[n / sps]) * env[n % sps]:
+//                   the carrier runs in ABSOLUTE time (phase-continuous; the
+//                   reference's PSK modulators restart it every symbol, which
+//                   decodes only where carrier / baud is an integer), so T0's
+//                   per-symbol w table does not apply; its env table does (all
+//                   ones when the 10 % ramp is empty).
+__device__ __forceinline__ int64_t tx_symbols8(int64_t nb) { return 40 + (8 * nb + 2) / 3; }
+
+__device__ __forceinline__ double tx_step8(uint32_t g, double ph) {
+  constexpr double kPi = 3.141592653589793;
+  const int m = (int)((g ^ (g >> 1) ^ (g >> 2)) & 7u);
+  return ph + (double)(m <= 4 ? m : m - 8) * (kPi / 4);
+}
+
+__global__ __launch_bounds__(64) void k_tx_phase8(const uint8_t* __restrict__ data, int64_t stride,
+                                                  const int64_t* __restrict__ n_bytes, int64_t n_streams, TxParams p,
+                                                  double* __restrict__ phase) {
+  const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+  if (s >= n_streams) return;
+  int64_t nb = n_bytes[s];
+  nb = nb < 0 ? 0 : (nb > stride ? stride : nb);
+  const uint8_t* __restrict__ d = data + s * stride;
+  const int64_t total = tx_symbols8(nb);
+  const int64_t n = total < p.sym_stride ? total : p.sym_stride;   // symbols stored
+  double* __restrict__ out = phase + s * p.sym_stride;
+  double ph = 0.0;
+  int64_t j = 0;
+  for (; j < 40 && j < n; ++j) {                   // [0,0,0]*30 + [1,1,0]*10
+    ph = tx_step8(j < 30 ? 0u : 6u, ph);
+    out[j] = ph;
+  }
+  for (int64_t q = 0; j < n; q += 3) {              // j = 40 + 8 q / 3: even, the pairs 16-B aligned
+    const uint32_t b0 = d[q];                        // q < nb: symbol j exists
+    const uint32_t b1 = q + 1 < nb ? d[q + 1] : 0u, b2 = q + 2 < nb ? d[q + 2] : 0u;
+    const uint32_t w = (b0 << 16) | (b1 << 8) | b2;
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      ph = tx_step8((w >> (21 - 3 * k)) & 7u, ph);
+      v[k] = ph;
+    }
+    if (j + 8 <= n) {
+#pragma unroll
+      for (int k = 0; k < 8; k += 2) *reinterpret_cast<double2*>(out + j + k) = make_double2(v[k], v[k + 1]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (j + k < n) out[j + k] = v[k];
+    }
+    j += 8;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_tx_synth8(const int64_t* __restrict__ n_bytes, int64_t stride, TxParams p,
+                                                   const double* __restrict__ phase, const double* __restrict__ tab,
+                                                   float* __restrict__ out, int64_t out_stride,
+                                                   int16_t* __restrict__ pcm, int64_t pcm_stride) {
+  const int64_t s = blockIdx.y;
+  int64_t nb = n_bytes[s];
+  nb = nb < 0 ? 0 : (nb > stride ? stride : nb);
+  const int64_t len = tx_symbols8(nb) * p.sps;
+  const double* __restrict__ ph = phase + s * p.sym_stride;
+  const double* __restrict__ env = tab + 2 * p.sps;
+  const uint32_t sps = (uint32_t)p.sps;
+  const int64_t k0 = (int64_t)blockIdx.x * 1024 + 4 * threadIdx.x;
+  if (k0 >= p.n_out) return;
+  uint32_t sym = (uint32_t)k0 / sps;
+  uint32_t i = (uint32_t)k0 - sym * sps;
+  float f[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    f[u] = 0.0f;
+    if (k0 + u < len && k0 + u < p.n_out) {
+      const double t = (double)(k0 + u) / p.fs;      // n / samp_rate
+      f[u] = (float)(sin(p.c0 * t + ph[sym]) * env[i]);
+    }
+    if (++i == sps) {
+      i = 0;
+      ++sym;
+    }
+  }
+  int16_t q[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) q[u] = (int16_t)(int)(f[u] * 32767.0f);   // (arr * 32767).astype(np.int16)
+  float* __restrict__ o = out + s * out_stride + k0;
+  int16_t* __restrict__ c = pcm ? pcm + s * pcm_stride + k0 : nullptr;
+  if (VEC && k0 + 4 <= p.n_out) {
+    *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
+    if (c) *reinterpret_cast<short4*>(c) = make_short4(q[0], q[1], q[2], q[3]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (k0 + u < p.n_out) {
+        o[u] = f[u];
+        if (c) c[u] = q[u];
+      }
+    }
+  }
+}
+
+static void launch_tx_d8psk(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
+                            int64_t n_streams, const double* tab, double* phase, float* out, int64_t out_stride,
+                            int16_t* pcm, int64_t pcm_stride, hipStream_t st) {
+  const dim3 pg((unsigned)((n_streams + kWave - 1) / kWave));
+  hipLaunchKernelGGL(k_tx_phase8, pg, dim3(kWave), 0, st, data, stride, n_bytes, n_streams, p, phase);
+  const dim3 sg((unsigned)((p.n_out + 1023) / 1024), (unsigned)n_streams);
+  const bool vec = (out_stride % 4) == 0 && ((uintptr_t)out % 16) == 0 &&
+                   (!pcm || ((pcm_stride % 4) == 0 && ((uintptr_t)pcm % 8) == 0));
+  if (vec)
+    hipLaunchKernelGGL((k_tx_synth8<true>), sg, dim3(256), 0, st, n_bytes, stride, p, phase, tab, out, out_stride, pcm,
+                       pcm_stride);
+  else
+    hipLaunchKernelGGL((k_tx_synth8<false>), sg, dim3(256), 0, st, n_bytes, stride, p, phase, tab, out, out_stride,
+                       pcm, pcm_stride);
+}
+
 // ---- AMR_TX_HELL: hellschreiber_modulate (hellschreiber.py:109-152) ----
 // The payload is one glyph index per character (0..94 = ' '..'~', kHellBlank
 // for a character outside the table: the host did the UTF-8 decode).  Pixels:
@@ -387,6 +515,8 @@ hipError_t launch_tx(const TxParams& p, const uint8_t* data, int64_t stride, con
     launch_tx_mode<AMR_TX_QPSK>(p, data, stride, n_bytes, n_streams, tab, phase, out, out_stride, pcm, pcm_stride, st);
   else if (p.mode == AMR_TX_BPSK)
     launch_tx_mode<AMR_TX_BPSK>(p, data, stride, n_bytes, n_streams, tab, phase, out, out_stride, pcm, pcm_stride, st);
+  else if (p.mode == AMR_TX_D8PSK)
+    launch_tx_d8psk(p, data, stride, n_bytes, n_streams, tab, phase, out, out_stride, pcm, pcm_stride, st);
   else
     launch_tx_mode<AMR_TX_FSK>(p, data, stride, n_bytes, n_streams, tab, phase, out, out_stride, pcm, pcm_stride, st);
   return hipGetLastError();

@@ -13,6 +13,10 @@ Receive side (the hot path, bit-exact with the reference):
 plus batched forms (*_demodulate_batch) that take a [B, N] array and return
 one bytes object per stream -- the form the GPU is built for.
 
+d8psk (no reference counterpart): a real 8-ary differential
+PSK modem, 3 bits per symbol, beside the psk8_* aliases the reference keeps:
+  d8psk_modulate, d8psk_demodulate (+ _batch, _soft, _soft_batch).
+
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
@@ -164,12 +168,45 @@ def bpsk_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, s
     return _psk_soft_batch("bpsk", np.asarray(samples), baud, carrier, samp_rate)
 
 
+# ---------------------------------------------------------------------------
+# d8psk: 8-ary differential PSK.  QPSK's front end (band-pass
+# carrier +- 1.5 baud, low-pass baud / nyquist, first sample at sps // 2), an
+# eight-sector slicer with Gray-coded tribits, the same sync search.
+def d8psk_demodulate(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000) -> bytes:
+    """8-ary differential PSK demodulation of one stream, on the GPU."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("d8psk_demodulate expects a 1-D sample array (use d8psk_demodulate_batch)")
+    return _psk_batch("d8psk", x[None, :], baud, carrier, samp_rate)[0]
+
+
+def d8psk_demodulate_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == d8psk_demodulate(row))."""
+    return _psk_batch("d8psk", np.asarray(samples), baud, carrier, samp_rate)
+
+
+def d8psk_demodulate_soft(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """d8psk_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes)).
+    Three values per symbol, b2, b1, b0; b0's magnitude tops out near 74, not 127
+    (its decision lines lie pi/4 apart, the other bits' pi/2)."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("d8psk_demodulate_soft expects a 1-D sample array (use d8psk_demodulate_soft_batch)")
+    outs, softs = _psk_soft_batch("d8psk", x[None, :], baud, carrier, samp_rate)
+    return outs[0], softs[0]
+
+
+def d8psk_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _psk_soft_batch("d8psk", np.asarray(samples), baud, carrier, samp_rate)
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):
     a stream keeps its own dtype (and with it its odd extension, _as_batch)
     rather than the one numpy would promote a mixed stack to."""
-    fn = {"qpsk": qpsk_demodulate_batch, "bpsk": bpsk_demodulate_batch}[kind]
+    fn = {"qpsk": qpsk_demodulate_batch, "bpsk": bpsk_demodulate_batch, "d8psk": d8psk_demodulate_batch}[kind]
     rows = [_as_batch(s) for s in streams]
     groups: dict = {}
     for i, r in enumerate(rows):
@@ -326,10 +363,17 @@ def fsk_modulate(data_bytes: bytes, baud=1200, mark_freq=1200.0, space_freq=2200
     return _amr.modulate(_amr.TX_FSK, [bytes(data_bytes)], baud, mark_freq, space_freq, samp_rate)[0]
 
 
+def d8psk_modulate(data_bytes: bytes, baud=1200, carrier=3000.0, samp_rate=96000) -> np.ndarray:
+    """8-ary differential PSK: [0,0,0]*30 + [1,1,0]*10 + the payload's
+    bits, three per symbol as a Gray-coded phase step of k * pi/4, on a
+    phase-continuous carrier; 40 + ceil(8 len / 3) symbols."""
+    return _amr.modulate(_amr.TX_D8PSK, [bytes(data_bytes)], baud, carrier, 0.0, samp_rate)[0]
+
+
 def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
     cut / zero-padded to n_out; default the longest), plus wav_from_array's
-    int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' (f0 = carrier) or
+    int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' | 'd8psk' (f0 = carrier) or
     'fsk' (f0 = mark_freq, f1 = space_freq), or 'hell' (datas: texts or UTF-8
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
     pass baud=122.5 for the reference's default)."""

@@ -91,7 +91,10 @@ extern "C" {
                                   amr_viterbi_work_bytes, amr_viterbi_decode_host / _device);
                                   amr_psk_plan_last_lowpass (AMR_LP_*); amr_sync_pack_host (diagnostic);
                                   the Reed-Solomon code (amr_rs_encoded_len, amr_rs_decoded_len,
-                                  amr_rs_encode_host / _device, amr_rs_decode_host / _device) */
+                                  amr_rs_encode_host / _device, amr_rs_decode_host / _device);
+                                  the 8-ary differential PSK modem: AMR_PSK_D8PSK (a plan kind,
+                                  and a kind of amr_psk_slice_host / amr_psk_soft_host) and
+                                  AMR_TX_D8PSK (a modulation mode) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -108,6 +111,17 @@ extern "C" {
 
 #define AMR_PSK_QPSK 0        /* DQPSK slicer, modem.py:216-241 */
 #define AMR_PSK_BPSK 1        /* DBPSK slicer, modem.py:102-105 */
+/* d8psk: 8-ary differential PSK, 3 bits per symbol (no reference counterpart:
+ * the reference's "8PSK" is a QPSK alias).  QPSK's filters,
+ * sps and first symbol; on d = s[k+1] * conj(s[k]) (numpy's multiply), with
+ * T = 0x1.a827999fcef32p-2 (tan(pi/8)), ar = |dr|, ai = |di|:
+ *   ai < T*ar: m = dr > 0 ? 0 : 4;  else ar < T*ai: m = di > 0 ? 2 : 6;
+ *   else m = di > 0 ? (dr > 0 ? 1 : 3) : (dr > 0 ? 7 : 5)
+ * and the bits are the Gray code m ^ (m >> 1), MSB first, 3 (S - 1) per stream
+ * in one contiguous string; sync search and byte pack as for the others.  A
+ * d8psk plan never runs the time-split layout (it takes the row layout
+ * instead) and its lane layout always slices in a kernel of its own. */
+#define AMR_PSK_D8PSK 2
 
 /* kernel timing slots reported by amr_psk_plan_timings() */
 #define AMR_T_BANDPASS 0
@@ -140,10 +154,10 @@ int amr_memcpy_d2d(void *dst, const void *src, int64_t bytes);
 int amr_device_synchronize(void);
 
 /* ---- DPSK demodulation ------------------------------------------------------
- * kind          AMR_PSK_QPSK | AMR_PSK_BPSK
+ * kind          AMR_PSK_QPSK | AMR_PSK_BPSK | AMR_PSK_D8PSK
  * n_samples     samples per stream (all streams of a call share it)
  * sps           int(fs / baud)                                 modem.py:70,191
- * first_symbol  sps // 2 (QPSK, modem.py:209) or sps (BPSK, modem.py:92)
+ * first_symbol  sps // 2 (QPSK, modem.py:209; d8psk) or sps (BPSK, modem.py:92)
  * bp_*          band-pass b, a, lfilter_zi (ntaps each; a[0] must be 1)
  * lp_*          low-pass  b, a, lfilter_zi
  * lo4           [n_samples][4] doubles: lo_re, lo_im, -(0*lo_im), 0*lo_re
@@ -590,6 +604,15 @@ int amr_frame_parse_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_s
  * ValueError (np.max of an empty waveform; < 0: np.zeros of a negative size):
  * AMR_E_INVALID with numpy's message.  n_bytes counts characters. */
 #define AMR_TX_HELL 3
+/* d8psk_modulate (no reference counterpart): the bits
+ * [0,0,0]*30 + [1,1,0]*10 + payload, zero-padded to a multiple of 3, taken
+ * three at a time (MSB first) as a Gray-coded phase step of k * pi/4,
+ * 40 + ceil(8 n_bytes / 3) symbols of sps = int(sample_rate / baud) samples:
+ *   out[n] = float32(sin(((2 pi) f0) * (n / sample_rate) + phase[n / sps]) * env[n % sps])
+ * -- the carrier runs in absolute time (phase-continuous), the envelope is the
+ * PSK modulators' 10 % ramps, all ones when the ramp is empty (sps < 10 is
+ * allowed); sps < 1 is AMR_E_INVALID. */
+#define AMR_TX_D8PSK 4
 /* natural waveform length of an n_bytes payload (the reference's len(out)), or < 0 */
 int64_t amr_tx_samples(int mode, int64_t n_bytes, double baud, double sample_rate);
 /* device scratch bytes amr_modulate_device needs for this shape */
