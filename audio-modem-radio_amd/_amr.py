@@ -74,7 +74,14 @@ EXPORTS = [
     "amr_viterbi_decode_soft_device", "amr_viterbi_decode_soft_host",
     "amr_rs_encoded_len", "amr_rs_decoded_len", "amr_rs_encode_host", "amr_rs_encode_device", "amr_rs_decode_host",
     "amr_rs_decode_device",
+    "amr_ofdm_plan_create", "amr_ofdm_plan_destroy", "amr_ofdm_plan_synchronize", "amr_ofdm_plan_enable_timing",
+    "amr_ofdm_plan_timings", "amr_ofdm_plan_out_capacity", "amr_ofdm_plan_scratch_bytes",
+    "amr_ofdm_plan_bytes_estimate", "amr_ofdm_demod_host", "amr_ofdm_demod_device", "amr_ofdm_demod_soft_host",
+    "amr_ofdm_demod_soft_device", "amr_ofdm_symbols_host", "amr_ofdm_slice_host", "amr_ofdm_soft_host",
+    "amr_ofdm_modulate_host",
 ]
+TO_NAMES = ["dft", "slice", "sync_pack", "launch"]
+OFDM_MAX_K = 64
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK = 0, 1, 2, 3, 4
 TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL, "d8psk": TX_D8PSK}
@@ -435,6 +442,22 @@ def lib():
             "amr_rs_encode_device": (I32, [P, P, I64, P, I64, I32, I32, P, I64, P]),
             "amr_rs_decode_host": (I32, [P, I64, P, P, I64, I32, I32, P, I64, P, P, P]),
             "amr_rs_decode_device": (I32, [P, P, I64, P, P, I64, I32, I32, P, I64, P, P, P]),
+            "amr_ofdm_plan_create": (I32, [P, I32, I64, I64, I32, P, P, I64]),
+            "amr_ofdm_plan_destroy": (I32, [P]),
+            "amr_ofdm_plan_synchronize": (I32, [P]),
+            "amr_ofdm_plan_enable_timing": (I32, [P, I32]),
+            "amr_ofdm_plan_timings": (I32, [P, P, I32]),
+            "amr_ofdm_plan_out_capacity": (I64, [P]),
+            "amr_ofdm_plan_scratch_bytes": (I64, [P]),
+            "amr_ofdm_plan_bytes_estimate": (I64, [I64, I64, I32, I64]),
+            "amr_ofdm_demod_host": (I32, [P, P, I32, I64, I64, P, I64, P, P]),
+            "amr_ofdm_demod_device": (I32, [P, P, I32, I64, I64, P, I64, P, P]),
+            "amr_ofdm_demod_soft_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64]),
+            "amr_ofdm_demod_soft_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64]),
+            "amr_ofdm_symbols_host": (I32, [P, P, I32, I64, I64, P]),
+            "amr_ofdm_slice_host": (I32, [P, I64, I64, I32, P]),
+            "amr_ofdm_soft_host": (I32, [P, I64, I64, I32, P]),
+            "amr_ofdm_modulate_host": (I32, [D, D, D, I32, P, I64, P, I64, P, I64, I64, P, I64]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -899,6 +922,212 @@ def get_psk_plan(kind: str, n: int, baud, carrier, samp_rate, batch: int) -> Psk
         return max(0, int(lib().amr_psk_plan_bytes_estimate(PSK_KINDS[kind], int(n), sps, first, 9, 5, m)))
     return plan_cache.get(key, need, lambda m: PskPlan(kind, n, baud, carrier, samp_rate, max_streams=m, device=dev),
                           estimate if sps >= 1 else None)
+
+
+# ---------------------------------------------------------------------------
+# ofdm: the multi-carrier DQPSK modem (tests/ofdm_cases.py)
+def ofdm_geometry(baud, carrier, num_subcarriers, samp_rate=96000):
+    """(sps, L, Ncp, Nu, bins int32 [K]) of DESIGN.md §3j, or ValueError when the
+    geometry is not valid (host arithmetic, before any device work)."""
+    K = int(num_subcarriers)
+    sps = int(samp_rate / baud)
+    if not 1 <= K <= OFDM_MAX_K:
+        raise ValueError(f"ofdm: num_subcarriers {K} outside [1, {OFDM_MAX_K}]")
+    if sps < 1:
+        raise ValueError("ofdm: fewer than one sample per dibit")
+    L = K * sps
+    Ncp = L // 8
+    Nu = L - Ncp
+    c0 = int(np.floor(float(carrier) * Nu / float(samp_rate) + 0.5))
+    bins = c0 - K // 2 + np.arange(K, dtype=np.int64)
+    if bins[0] < 1:
+        raise ValueError(f"ofdm: lowest subcarrier on bin {int(bins[0])}, below bin 1")
+    if 2 * bins[-1] >= Nu:
+        raise ValueError(f"ofdm: highest subcarrier on bin {int(bins[-1])}, at or above Nu / 2 = {Nu} / 2")
+    return sps, L, Ncp, Nu, bins.astype(np.int32)
+
+
+def design_ofdm(baud, carrier, num_subcarriers, samp_rate=96000):
+    """The geometry and the twiddle table W [K][Nu][2] float64, (cos th, -sin th)
+    with th = (2 pi) * (((bins[k] * m) % Nu) / Nu): what the plan takes, and what
+    tests/ofdm_cases.py correlates against."""
+    sps, L, Ncp, Nu, bins = ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)
+    r = (bins.astype(np.int64)[:, None] * np.arange(Nu, dtype=np.int64)[None, :]) % Nu
+    th = (2 * np.pi) * (r / Nu)
+    W = np.ascontiguousarray(np.stack([np.cos(th), -np.sin(th)], axis=-1), np.float64)
+    return sps, L, Ncp, Nu, bins, W
+
+
+def _rows(x: np.ndarray):
+    """(x, row stride in elements): rows of a wider array go as they are."""
+    B, n = x.shape
+    if x.strides[1] != x.itemsize or (B > 1 and (x.strides[0] % x.itemsize or x.strides[0] < n * x.itemsize)):
+        x = np.ascontiguousarray(x)
+    return x, (x.strides[0] // x.itemsize if B > 1 else n)
+
+
+class OfdmPlan:
+    """A device plan of the ofdm demodulator: W in HBM + Y and the bit words for max_streams streams."""
+
+    def __init__(self, n: int, baud, carrier, num_subcarriers, samp_rate=96000, max_streams=64, device=None):
+        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
+        self.sps, self.L, self.Ncp, self.Nu, self.bins, W = design_ofdm(baud, carrier, num_subcarriers, samp_rate)
+        self.K = len(self.bins)
+        self.S = self.n // self.L
+        require_gpu()
+        self.device = default_device() if device is None else device
+        self.max_streams = int(max_streams)
+        h = ctypes.c_void_p()
+        check(lib().amr_ofdm_plan_create(ctypes.byref(h), self.device, self.n, self.sps, self.K, ptr(self.bins),
+                                         ptr(W), self.max_streams))
+        self.handle = h
+        self.out_cap = int(lib().amr_ofdm_plan_out_capacity(h))
+        self.lock = threading.Lock()
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and _lib is not None:
+            try:
+                _lib.amr_ofdm_plan_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _batches(self, x):
+        x, stride = _rows(x)
+        for s0 in range(0, x.shape[0], self.max_streams):
+            yield s0, x[s0:s0 + self.max_streams], stride
+
+    def demod_host(self, x: np.ndarray):
+        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync)."""
+        outs, syncs = [], np.empty(x.shape[0], np.int64)
+        cap = max(self.out_cap, 1)
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            ln = np.empty(nb, np.int64)
+            sy = np.empty(nb, np.int64)
+            with self.lock:
+                check(lib().amr_ofdm_demod_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
+                                                ptr(ln), ptr(sy)))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+        return outs, syncs
+
+    def demod_soft_host(self, x: np.ndarray):
+        """demod_host with the soft values: (list[bytes], sync, list[int8 array]);
+        soft[i][j] belongs to bit j of outs[i]."""
+        outs, softs, syncs = [], [], np.empty(x.shape[0], np.int64)
+        cap = max(self.out_cap, 1)
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            soft = np.empty((nb, 8 * cap), np.int8)
+            ln = np.empty(nb, np.int64)
+            sy = np.empty(nb, np.int64)
+            with self.lock:
+                check(lib().amr_ofdm_demod_soft_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out),
+                                                     cap, ptr(ln), ptr(sy), ptr(soft), 8 * cap))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            softs += [soft[i, :8 * ln[i]].copy() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+        return outs, syncs, softs
+
+    def symbols(self, x: np.ndarray) -> np.ndarray:
+        """The DFT stage alone (amr_ofdm_symbols_host): Y [B][S][K] complex128."""
+        Y = np.zeros((x.shape[0], self.S, self.K, 2))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            yb = np.zeros((nb, self.S, self.K, 2))
+            with self.lock:
+                check(lib().amr_ofdm_symbols_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(yb)))
+            Y[s0:s0 + nb] = yb
+        return Y.view(np.complex128)[..., 0]
+
+    def scratch_bytes(self) -> int:
+        """Device bytes this plan holds (W, Y, words + host-API staging)."""
+        return int(lib().amr_ofdm_plan_scratch_bytes(self.handle)) if self.handle else 0
+
+    def enable_timing(self, on=True):
+        check(lib().amr_ofdm_plan_enable_timing(self.handle, 1 if on else 0))
+
+    def synchronize(self):
+        check(lib().amr_ofdm_plan_synchronize(self.handle))
+
+    def timings(self) -> dict:
+        ms = (ctypes.c_float * len(TO_NAMES))()
+        check(lib().amr_ofdm_plan_timings(self.handle, ms, len(TO_NAMES)))
+        return {k: float(v) for k, v in zip(TO_NAMES, ms) if v >= 0}
+
+
+def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int) -> OfdmPlan:
+    """The shared plan cache, keyed by the call's parameters (and device)."""
+    dev = default_device()
+    K = int(num_subcarriers)
+    key = ("ofdm", int(n), float(baud), float(carrier), K, float(samp_rate), dev)
+    need = stream_bucket(batch, PSK_MAX_CHUNK)
+    sps, *_ = ofdm_geometry(baud, carrier, K, samp_rate)                # ValueError before any plan is evicted
+
+    def estimate(m):
+        return max(0, int(lib().amr_ofdm_plan_bytes_estimate(int(n), sps, K, m)))
+    return plan_cache.get(key, need, lambda m: OfdmPlan(n, baud, carrier, K, samp_rate, max_streams=m, device=dev),
+                          estimate)
+
+
+def ofdm_tx_samples(n_bytes: int, baud, carrier, num_subcarriers, samp_rate=96000) -> int:
+    """len() of ofdm_modulate's output for an n_bytes payload: (1 + ceil((40 + 4 n) / K)) * L."""
+    _, L, _, _, bins = ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)
+    K = len(bins)
+    return (1 + -(-(40 + 4 * int(n_bytes)) // K)) * L
+
+
+def ofdm_modulate(datas, baud, carrier, num_subcarriers, samp_rate=96000, n_out=None, pcm=False):
+    """Batched ofdm modulator on the GPU (amr_ofdm_modulate_host): [B][n_out]
+    float32, cut / zero-padded to n_out (default: the longest natural length);
+    pcm=True also returns wav_from_array's int16."""
+    K = int(num_subcarriers)
+    n = len(datas)
+    lens = np.array([len(d) for d in datas], np.int64)
+    natural = [ofdm_tx_samples(int(v), baud, carrier, K, samp_rate) for v in lens]     # the geometry's ValueError
+    ofdm_geometry(baud, carrier, K, samp_rate)
+    require_gpu()
+    if n_out is None:
+        n_out = max(natural, default=0)
+    stride = max(1, int(lens.max()) if n else 1)
+    buf = np.zeros((max(n, 1), stride), np.uint8)
+    for i, d in enumerate(datas):
+        buf[i, :len(d)] = np.frombuffer(bytes(d), np.uint8)
+    out = np.zeros((n, n_out), np.float32)
+    pc = np.zeros((n, n_out), np.int16) if pcm else None
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_ofdm_modulate_host(float(baud), float(carrier), float(samp_rate), K, ptr(buf), stride, ptr(lens),
+                                       n, ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out))
+    return (out, pc) if pcm else out
+
+
+def ofdm_slice(Y: np.ndarray) -> np.ndarray:
+    """The slicer stage alone on the GPU (k_ofdm_slice): Y [B][S][K] complex128 ->
+    the decided bits [B][2 K (S - 1)] as uint8."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S, K = Y.shape
+    nbits = max(0, 2 * K * (S - 1))
+    nw = max(1, (nbits + 31) // 32)
+    words = np.zeros((B, nw), np.uint32)
+    check(lib().amr_ofdm_slice_host(ptr(Y), B, S, K, ptr(words)))
+    bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
+    return bits[:, :nbits]
+
+
+def ofdm_soft(Y: np.ndarray) -> np.ndarray:
+    """The soft stage alone on the GPU (k_ofdm_slice then k_ofdm_soft): Y [B][S][K]
+    complex128 -> int8 [B][2 K (S - 1)], one value per decided bit from bit 0."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S, K = Y.shape
+    soft = np.zeros((B, max(0, 2 * K * (S - 1))), np.int8)
+    check(lib().amr_ofdm_soft_host(ptr(Y), B, S, K, ptr(soft)))
+    return soft
 
 
 def fec_decode_host(datas):

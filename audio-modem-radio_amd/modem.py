@@ -17,6 +17,10 @@ d8psk (no reference counterpart): a real 8-ary differential
 PSK modem, 3 bits per symbol, beside the psk8_* aliases the reference keeps:
   d8psk_modulate, d8psk_demodulate (+ _batch, _soft, _soft_batch).
 
+ofdm (no reference counterpart): a real multi-carrier DQPSK
+modem beside the ofdm_*_simple aliases the reference keeps:
+  ofdm_modulate, ofdm_demodulate (+ _batch, _soft, _soft_batch).
+
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
@@ -201,6 +205,60 @@ def d8psk_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, 
     return _psk_soft_batch("d8psk", np.asarray(samples), baud, carrier, samp_rate)
 
 
+# ---------------------------------------------------------------------------
+# ofdm: multi-carrier DQPSK.  K subcarriers on exact DFT bins
+# of the useful part of an OFDM symbol of K * sps samples (an eighth of it the
+# cyclic prefix), each carrying DQPSK across time: no filters, one dense FP64
+# correlation against a twiddle table, the QPSK sync search.  Samples are
+# float32, float64 or int16 PCM (read as int16 / 32768); anything else goes
+# as float64.
+def _ofdm_input(samples) -> np.ndarray:
+    x = np.asarray(samples)
+    return x if x.dtype in _amr.DTYPES else x.astype(np.float64)
+
+
+def _ofdm_batch(x2d, baud, carrier, num_subcarriers, samp_rate, soft=False):
+    x2d = _ofdm_input(x2d)
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    B, n = x2d.shape
+    _amr.ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)      # ValueError, also for an empty batch
+    if B == 0:
+        return ([], []) if soft else []
+    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B)
+    if soft:
+        outs, _, softs = plan.demod_soft_host(x2d)
+        return outs, softs
+    return plan.demod_host(x2d)[0]
+
+
+def ofdm_demodulate(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> bytes:
+    """Multi-carrier DQPSK demodulation of one stream, on the GPU."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("ofdm_demodulate expects a 1-D sample array (use ofdm_demodulate_batch)")
+    return _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate)[0]
+
+
+def ofdm_demodulate_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == ofdm_demodulate(row))."""
+    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate)
+
+
+def ofdm_demodulate_soft(samples, baud, carrier, num_subcarriers, samp_rate=96000):
+    """ofdm_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("ofdm_demodulate_soft expects a 1-D sample array (use ofdm_demodulate_soft_batch)")
+    outs, softs = _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, soft=True)
+    return outs[0], softs[0]
+
+
+def ofdm_demodulate_soft_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, soft=True)
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):
@@ -370,13 +428,28 @@ def d8psk_modulate(data_bytes: bytes, baud=1200, carrier=3000.0, samp_rate=96000
     return _amr.modulate(_amr.TX_D8PSK, [bytes(data_bytes)], baud, carrier, 0.0, samp_rate)[0]
 
 
-def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False):
+def ofdm_modulate(data_bytes: bytes, baud, carrier, num_subcarriers, samp_rate=96000) -> np.ndarray:
+    """Multi-carrier DQPSK: [0,0]*30 + [1,1]*10 + the payload's bits,
+    zero-padded to a multiple of 2 K; dibit j on OFDM symbol 1 + j // K, subcarrier
+    j % K, as a phase step from the symbol before; symbol 0 carries the Newman
+    reference phases.  (1 + ceil((40 + 4 len) / K)) * K * sps samples."""
+    return _amr.ofdm_modulate([bytes(data_bytes)], baud, carrier, num_subcarriers, samp_rate)[0]
+
+
+def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False,
+                   num_subcarriers=None):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
     cut / zero-padded to n_out; default the longest), plus wav_from_array's
     int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' | 'd8psk' (f0 = carrier) or
     'fsk' (f0 = mark_freq, f1 = space_freq), or 'hell' (datas: texts or UTF-8
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
-    pass baud=122.5 for the reference's default)."""
+    pass baud=122.5 for the reference's default), or 'ofdm' (f0 = carrier,
+    num_subcarriers required)."""
+    if kind == "ofdm":
+        if num_subcarriers is None:
+            raise ValueError("modulate_batch('ofdm', ...) needs num_subcarriers")
+        return _amr.ofdm_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, num_subcarriers,
+                                  samp_rate, n_out, pcm)
     mode = _amr.TX_MODES[kind]
     if kind == "hell":
         _hell_sps(baud, samp_rate, tx=True)

@@ -94,7 +94,8 @@ extern "C" {
                                   amr_rs_encode_host / _device, amr_rs_decode_host / _device);
                                   the 8-ary differential PSK modem: AMR_PSK_D8PSK (a plan kind,
                                   and a kind of amr_psk_slice_host / amr_psk_soft_host) and
-                                  AMR_TX_D8PSK (a modulation mode) */
+                                  AMR_TX_D8PSK (a modulation mode); the multi-carrier DQPSK
+                                  modem (amr_ofdm_*, AMR_TO_*) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -779,6 +780,79 @@ int amr_rs_decode_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_str
 int amr_rs_decode_host(const uint8_t *in, int64_t in_stride, const int64_t *in_len, const uint8_t *erase, int64_t n,
                        int nsym, int interleave, uint8_t *out, int64_t out_stride, int64_t *out_len,
                        int32_t *corrected, int32_t *failed);
+
+/* ---- ofdm: a multi-carrier DQPSK modem (no reference counterpart: the
+ * reference's ofdm_*_simple ignore num_subcarriers and call QPSK; DESIGN.md
+ * §3j, tests/ofdm_cases.py) ---------------------------------------------------
+ * Geometry for (sps, K): one OFDM symbol is L = K * sps samples, the cyclic
+ * prefix Ncp = L / 8 of them, Nu = L - Ncp the useful part; subcarrier k sits
+ * on DFT bin bins[k] = bins[0] + k of the Nu useful samples.  Valid iff
+ * 1 <= K <= 64, sps >= 1, bins[0] >= 1 and 2 * bins[K-1] < Nu; anything else
+ * is AMR_E_INVALID before any device work.
+ * W: the caller's twiddle table [K][Nu][2] float64, (cos th, -sin th) with
+ * th = (2 pi) * (((bins[k] * m) % Nu) / Nu).
+ * Receiver: S = n_samples / L symbols per stream (a partial tail is ignored),
+ *   Y[s][k] = sum_m x[s*L + Ncp + m] * W[k][m]      in four interleaved partial
+ * sums p[m & 3], each sequential in m from 0.0, every product rounded before
+ * it is added (no fma), combined as (p0 + p1) + (p2 + p3) per component;
+ * d = Y[s+1][k] * conj(Y[s][k]) (numpy's multiply, as the PSK slicers), and
+ * with ar = |dr|, ai = |di|:  ai < ar: m = dr > 0 ? 0 : 2;  else m = di > 0 ?
+ * 1 : 3;  the dibit is {0, 1, 3, 2}[m], MSB first, in the order j = s*K + k:
+ * 2 K (S - 1) bits per stream in one string; sync search and byte pack as for
+ * the PSK plans.  S < 2: no bytes, sync index -1.
+ * Soft values: two int8 per product, the hard bit's sign, the magnitudes of
+ * amr_psk_soft_host's QPSK rule, aligned to the bytes as amr_psk_demod_soft_*. */
+typedef struct amr_ofdm_plan amr_ofdm_plan;
+#define AMR_TO_DFT 0          /* k_ofdm_dft */
+#define AMR_TO_SLICE 1        /* k_ofdm_slice */
+#define AMR_TO_SYNC_PACK 2    /* sync search and byte pack; in a soft call k_ofdm_soft too (it reads their window) */
+#define AMR_TO_LAUNCH 3       /* the whole launch */
+#define AMR_TO_COUNT 4
+int amr_ofdm_plan_create(amr_ofdm_plan **plan, int device, int64_t n_samples, int64_t sps, int K,
+                         const int32_t *bins, const double *W, int64_t max_streams);
+int amr_ofdm_plan_destroy(amr_ofdm_plan *plan);
+int amr_ofdm_plan_synchronize(amr_ofdm_plan *plan);
+int amr_ofdm_plan_enable_timing(amr_ofdm_plan *plan, int on);
+/* milliseconds of each AMR_TO_* slot in the last call (-1 = not run) */
+int amr_ofdm_plan_timings(amr_ofdm_plan *plan, float *ms, int count);
+/* bytes an output row needs (2 K (S - 1) / 8 + 1), or -1 */
+int64_t amr_ofdm_plan_out_capacity(const amr_ofdm_plan *plan);
+/* device bytes the plan holds now, and (host arithmetic) what a plan of this
+ * shape holds once its host entries have staged a full batch; < 0: bad shape */
+int64_t amr_ofdm_plan_scratch_bytes(const amr_ofdm_plan *plan);
+int64_t amr_ofdm_plan_bytes_estimate(int64_t n_samples, int64_t sps, int K, int64_t max_streams);
+/* the PSK entries' shapes: x [n_streams][x_stride] samples of `dtype`, out
+ * [n_streams][out_stride] bytes (out_stride >= out_capacity - 1), lengths and
+ * sync indices; soft [n_streams][soft_stride], soft_stride >= 8 * out_capacity */
+int amr_ofdm_demod_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                        uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx);
+int amr_ofdm_demod_device(amr_ofdm_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                          uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx);
+int amr_ofdm_demod_soft_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                             uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx, int8_t *soft,
+                             int64_t soft_stride);
+int amr_ofdm_demod_soft_device(amr_ofdm_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                               uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                               int8_t *d_soft, int64_t soft_stride);
+/* the DFT stage alone: Y [n_streams][S][K][2] float64 (re, im) */
+int amr_ofdm_symbols_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                          double *Y);
+/* the slicer and soft stages alone on given Y [n_streams][n_sym][K][2]: words
+ * [n_streams][max(1, ceil(2 K (n_sym - 1) / 32))] (MSB first), soft
+ * [n_streams][2 K (n_sym - 1)] (every bit from 0) */
+int amr_ofdm_slice_host(const double *Y, int64_t n_streams, int64_t n_sym, int K, uint32_t *words);
+int amr_ofdm_soft_host(const double *Y, int64_t n_streams, int64_t n_sym, int K, int8_t *soft);
+/* ofdm_modulate: the bits [0,0]*30 + [1,1]*10 + payload, zero-padded to a
+ * multiple of 2 K; dibit j on symbol 1 + j / K, subcarrier j % K, as a phase
+ * step 00 -> 0, 01 -> pi/2, 11 -> pi, 10 -> -pi/2 added sequentially to symbol
+ * 0's Newman phases (pi * (k*k)) / K.  The geometry from sps = int(sample_rate
+ * / baud) and c0 = floor(carrier * Nu / sample_rate + 0.5), bins[k] = c0 - K/2
+ * + k.  Sample i of symbol s, m = (i - Ncp) mod Nu:
+ *   float32((sum_k sin((2 pi) * (((bins[k]*m) % Nu) / Nu) + ph[s][k])) * (1.0 / K))
+ * the sum sequential in k from 0.0.  out / pcm / n_out as amr_modulate_host. */
+int amr_ofdm_modulate_host(double baud, double carrier, double sample_rate, int K, const uint8_t *data,
+                           int64_t data_stride, const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride,
+                           int64_t n_out, int16_t *pcm, int64_t pcm_stride);
 
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
