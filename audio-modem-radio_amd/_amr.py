@@ -78,9 +78,11 @@ EXPORTS = [
     "amr_ofdm_plan_timings", "amr_ofdm_plan_out_capacity", "amr_ofdm_plan_scratch_bytes",
     "amr_ofdm_plan_bytes_estimate", "amr_ofdm_demod_host", "amr_ofdm_demod_device", "amr_ofdm_demod_soft_host",
     "amr_ofdm_demod_soft_device", "amr_ofdm_symbols_host", "amr_ofdm_slice_host", "amr_ofdm_soft_host",
-    "amr_ofdm_modulate_host",
+    "amr_ofdm_modulate_host", "amr_ofdm_acquire_bytes_estimate", "amr_ofdm_acquire_host", "amr_ofdm_acquire_device",
+    "amr_ofdm_symbols_at_host", "amr_ofdm_demod_acq_host", "amr_ofdm_demod_acq_device",
 ]
 TO_NAMES = ["dft", "slice", "sync_pack", "launch"]
+TO_SLOTS = TO_NAMES + ["acquire"]                  # AMR_TO_*: "acquire" is run by an acquiring call only
 OFDM_MAX_K = 64
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK = 0, 1, 2, 3, 4
@@ -458,6 +460,12 @@ def lib():
             "amr_ofdm_slice_host": (I32, [P, I64, I64, I32, P]),
             "amr_ofdm_soft_host": (I32, [P, I64, I64, I32, P]),
             "amr_ofdm_modulate_host": (I32, [D, D, D, I32, P, I64, P, I64, P, I64, I64, P, I64]),
+            "amr_ofdm_acquire_bytes_estimate": (I64, [I64, I64, I32, I64]),
+            "amr_ofdm_acquire_host": (I32, [P, P, I32, I64, I64, P, P, P]),
+            "amr_ofdm_acquire_device": (I32, [P, P, I32, I64, I64, P, P, P]),
+            "amr_ofdm_symbols_at_host": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_ofdm_demod_acq_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P]),
+            "amr_ofdm_demod_acq_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -866,6 +874,12 @@ class PlanCache:
             self._evict(reserve=0, keep=key)
             return pl
 
+    def reserve(self, key, nbytes: int):
+        """Room for `nbytes` more that the plan under `key` is about to allocate: other plans are evicted
+        until they fit beside the rest within the budget."""
+        with self.lock:
+            self._evict(reserve=int(nbytes), keep=key)
+
     def total_bytes(self) -> int:
         with self.lock:
             return self._total_unlocked()
@@ -998,8 +1012,12 @@ class OfdmPlan:
         for s0 in range(0, x.shape[0], self.max_streams):
             yield s0, x[s0:s0 + self.max_streams], stride
 
-    def demod_host(self, x: np.ndarray):
-        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync)."""
+    def demod_host(self, x: np.ndarray, acquire=False):
+        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync);
+        acquire=True: each stream from its own acquired offset, (list[bytes], sync, offsets)."""
+        if acquire:
+            outs, syncs, _, offs = self.demod_acq_host(x)
+            return outs, syncs, offs
         outs, syncs = [], np.empty(x.shape[0], np.int64)
         cap = max(self.out_cap, 1)
         for s0, xb, stride in self._batches(x):
@@ -1014,9 +1032,11 @@ class OfdmPlan:
             syncs[s0:s0 + nb] = sy
         return outs, syncs
 
-    def demod_soft_host(self, x: np.ndarray):
+    def demod_soft_host(self, x: np.ndarray, acquire=False):
         """demod_host with the soft values: (list[bytes], sync, list[int8 array]);
-        soft[i][j] belongs to bit j of outs[i]."""
+        soft[i][j] belongs to bit j of outs[i].  acquire=True: the offsets as a fourth value."""
+        if acquire:
+            return self.demod_acq_host(x, soft=True)
         outs, softs, syncs = [], [], np.empty(x.shape[0], np.int64)
         cap = max(self.out_cap, 1)
         for s0, xb, stride in self._batches(x):
@@ -1044,8 +1064,56 @@ class OfdmPlan:
             Y[s0:s0 + nb] = yb
         return Y.view(np.complex128)[..., 0]
 
+    def demod_acq_host(self, x: np.ndarray, soft=False):
+        """Acquisition, then the demodulation of every stream from its offset (amr_ofdm_demod_acq_host):
+        (list[bytes], sync, list[int8 array] or None, offsets int64 [B])."""
+        outs, softs = [], []
+        syncs, offs = np.empty(x.shape[0], np.int64), np.empty(x.shape[0], np.int64)
+        cap = max(self.out_cap, 1)
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            sv = np.empty((nb, 8 * cap), np.int8) if soft else None
+            ln, sy, of = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty(nb, np.int64)
+            with self.lock:
+                check(lib().amr_ofdm_demod_acq_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
+                                                    ptr(ln), ptr(sy), ptr(sv) if soft else None, 8 * cap, ptr(of)))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            if soft:
+                softs += [sv[i, :8 * ln[i]].copy() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+            offs[s0:s0 + nb] = of
+        return outs, syncs, (softs if soft else None), offs
+
+    def acquire(self, x: np.ndarray):
+        """The acquisition stage alone (amr_ofdm_acquire_host): (offset int64 [B], dhat int64 [B], E float64 [B][L])."""
+        B = x.shape[0]
+        off, dh, E = np.empty(B, np.int64), np.empty(B, np.int64), np.empty((B, self.L))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            of, d, e = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty((nb, self.L))
+            with self.lock:
+                check(lib().amr_ofdm_acquire_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(of), ptr(d),
+                                                  ptr(e)))
+            off[s0:s0 + nb], dh[s0:s0 + nb], E[s0:s0 + nb] = of, d, e
+        return off, dh, E
+
+    def symbols_at(self, x: np.ndarray, offsets) -> np.ndarray:
+        """The DFT stage at given per-stream offsets (amr_ofdm_symbols_at_host): Y [B][S][K] complex128."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        Y = np.zeros((x.shape[0], self.S, self.K, 2))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            yb = np.zeros((nb, self.S, self.K, 2))
+            ob = np.ascontiguousarray(offsets[s0:s0 + nb])
+            with self.lock:
+                check(lib().amr_ofdm_symbols_at_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(ob),
+                                                     ptr(yb)))
+            Y[s0:s0 + nb] = yb
+        return Y.view(np.complex128)[..., 0]
+
     def scratch_bytes(self) -> int:
-        """Device bytes this plan holds (W, Y, words + host-API staging)."""
+        """Device bytes this plan holds (W, Y, words + host-API staging + the acquisition buffers once used)."""
         return int(lib().amr_ofdm_plan_scratch_bytes(self.handle)) if self.handle else 0
 
     def enable_timing(self, on=True):
@@ -1055,13 +1123,14 @@ class OfdmPlan:
         check(lib().amr_ofdm_plan_synchronize(self.handle))
 
     def timings(self) -> dict:
-        ms = (ctypes.c_float * len(TO_NAMES))()
-        check(lib().amr_ofdm_plan_timings(self.handle, ms, len(TO_NAMES)))
-        return {k: float(v) for k, v in zip(TO_NAMES, ms) if v >= 0}
+        ms = (ctypes.c_float * len(TO_SLOTS))()
+        check(lib().amr_ofdm_plan_timings(self.handle, ms, len(TO_SLOTS)))
+        return {k: float(v) for k, v in zip(TO_SLOTS, ms) if v >= 0}
 
 
-def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int) -> OfdmPlan:
-    """The shared plan cache, keyed by the call's parameters (and device)."""
+def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int, acquire=False) -> OfdmPlan:
+    """The shared plan cache, keyed by the call's parameters (and device).  acquire: the plan is about to
+    acquire; the first time, the cache makes room for its acquisition buffers (amr_ofdm_acquire_bytes_estimate)."""
     dev = default_device()
     K = int(num_subcarriers)
     key = ("ofdm", int(n), float(baud), float(carrier), K, float(samp_rate), dev)
@@ -1070,8 +1139,12 @@ def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int)
 
     def estimate(m):
         return max(0, int(lib().amr_ofdm_plan_bytes_estimate(int(n), sps, K, m)))
-    return plan_cache.get(key, need, lambda m: OfdmPlan(n, baud, carrier, K, samp_rate, max_streams=m, device=dev),
-                          estimate)
+    pl = plan_cache.get(key, need, lambda m: OfdmPlan(n, baud, carrier, K, samp_rate, max_streams=m, device=dev),
+                        estimate)
+    if acquire and not getattr(pl, "acquires", False):
+        plan_cache.reserve(key, max(0, int(lib().amr_ofdm_acquire_bytes_estimate(int(n), sps, K, pl.max_streams))))
+        pl.acquires = True
+    return pl
 
 
 def ofdm_tx_samples(n_bytes: int, baud, carrier, num_subcarriers, samp_rate=96000) -> int:

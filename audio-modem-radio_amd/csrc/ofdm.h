@@ -1,5 +1,5 @@
-// ofdm.h -- the multi-carrier DQPSK modem (DESIGN.md §3j): what
-// ofdm_kernels.hip and ofdm_api.cpp share.
+// ofdm.h -- the multi-carrier DQPSK modem (DESIGN.md §3j, §3k): what
+// ofdm_kernels.hip, ofdm_acq_kernels.hip and ofdm_api.cpp share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,27 @@ hipError_t launch_ofdm_slice(const double* Y, int64_t n_streams, const OfdmParam
 hipError_t launch_ofdm_soft(const double* Y, int64_t n_streams, const OfdmParams& p, const uint32_t* words,
                             const int64_t* sync_idx, const int64_t* out_len, int8_t* soft, int64_t soft_stride,
                             hipStream_t st);
+
+// ---- acquisition (ofdm_acq_kernels.hip) -----------------------
+constexpr int kAcqSeg = 64;   // periods per segment of the fold
+// M = (n - Nu) / L periods take part in the fold (0 when n < Nu + L); its segments
+inline int64_t ofdm_acq_periods(const OfdmParams& p) { return p.n >= p.nu + p.L ? (p.n - p.nu) / p.L : 0; }
+inline int64_t ofdm_acq_segments(const OfdmParams& p) { return (ofdm_acq_periods(p) + kAcqSeg - 1) / kAcqSeg; }
+// the plan's work buffers of one acquiring call, all device memory
+struct OfdmAcq {
+  double* gq;         // [n_streams][segments][L]: the fold's partial sums
+  double* G;          // [n_streams][L]
+  double* E;          // [n_streams][L]
+  int64_t* dhat;      // [n_streams]: the first minimum of E
+  int64_t* offset;    // [n_streams]: dhat backed off by Ncp / 2, in [-Ncp, L - 1 - Ncp]
+};
+// fold, segment sum, window sum, first minimum and back-off of every stream
+hipError_t launch_ofdm_acquire(const void* x, int dtype, int64_t x_stride, int64_t n_streams, const OfdmParams& p,
+                               const OfdmAcq& a, hipStream_t st);
+// launch_ofdm_dft with stream b read from sample offset[b] on (device array, each
+// value in [-Ncp, L - 1 - Ncp]); samples at or past n count as 0.0 and are not loaded
+hipError_t launch_ofdm_dft_at(const void* x, int dtype, int64_t x_stride, int64_t n_streams, const OfdmParams& p,
+                              const double* W, const int64_t* offset, double* Y, hipStream_t st);
 
 // transmit: one modulate call
 struct OfdmTx {

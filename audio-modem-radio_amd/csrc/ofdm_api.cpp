@@ -1,7 +1,9 @@
 // ofdm_api.cpp -- C ABI of the multi-carrier DQPSK modem (include/amr.h,
 // DESIGN.md §3j): amr_ofdm_plan on PlanCore with dev_mem.h ownership, the
 // demodulation entries in the PSK entries' shape, the stage entries the tests
-// pin the kernels with, and the modulator.  The kernels are ofdm_kernels.hip.
+// pin the kernels with, the modulator, and acquisition (§3k: the work buffers,
+// the stage entries and the acquired demodulation).  The kernels are
+// ofdm_kernels.hip and ofdm_acq_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +36,8 @@ struct amr_ofdm_plan : PlanCore<AMR_TO_COUNT> {
     // staging for the host entries (lazily sized)
     DevBuf d_x;
     DevBuf d_out, d_len, d_sync;   // one group: all three or none (reserve_all)
+    // acquisition, from the first acquiring call on: one group
+    DevBuf gq, G, E, dhat, off;    // [ms][segments][L], [ms][L], [ms][L], [ms], [ms]
   } mem;
 };
 
@@ -74,6 +78,11 @@ int64_t staging_bytes(const OfdmParams& p, int64_t ms) {
   return std::max<int64_t>(ms * p.n * 8, 8) + ms * (p.n_bits / 8 + 1) + 2 * ms * 8;
 }
 
+// what the acquisition group holds: the fold's segment sums, G, E, dhat and the offsets
+int64_t acq_bytes(const OfdmParams& p, int64_t ms) {
+  return std::max<int64_t>(ms * ofdm_acq_segments(p) * p.L * 8, 8) + 2 * ms * p.L * 8 + 2 * ms * 8;
+}
+
 // set device, drain the stream, drop the gather gate; then the buffers; then events and the stream
 void ofdm_plan_free(amr_ofdm_plan* pl) {
   if (!pl) return;
@@ -86,15 +95,45 @@ void ofdm_plan_free(amr_ofdm_plan* pl) {
   delete pl;
 }
 
+// the acquisition group, allocated on the first acquiring call (all or nothing)
+int ofdm_acq_reserve(amr_ofdm_plan* pl) {
+  const int64_t ms = pl->max_streams, L = pl->p.L;
+  amr_ofdm_plan::Mem& m = pl->mem;
+  HIP_TRY((reserve_all({{m.gq, std::max<int64_t>(ms * ofdm_acq_segments(pl->p) * L * 8, 8)},
+                        {m.G, ms * L * 8},
+                        {m.E, ms * L * 8},
+                        {m.dhat, ms * 8},
+                        {m.off, ms * 8}},
+                       pl->stream)));
+  return AMR_OK;
+}
+
+// the acquisition kernels of one batch on the plan's stream, into mem.E / dhat / off
+int run_acquire(amr_ofdm_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride) {
+  if (int rc = ofdm_acq_reserve(pl)) return rc;
+  amr_ofdm_plan::Mem& m = pl->mem;
+  const OfdmAcq a{m.gq.as<double>(), m.G.as<double>(), m.E.as<double>(), m.dhat.as<int64_t>(), m.off.as<int64_t>()};
+  HIP_TRY_TIMED(*pl, AMR_TO_ACQUIRE, launch_ofdm_acquire(d_x, dtype, x_stride, B, pl->p, a, pl->stream));
+  return AMR_OK;
+}
+
 // One batch on the plan's stream (device pointers; the caller holds mu and
 // has set the device).  soft: non-null, k_ofdm_soft behind the sync search.
-int run_ofdm(amr_ofdm_plan* pl, const DemodIo& io, int8_t* soft, int64_t soft_stride) {
+// acquire: the streams' offsets first (run_acquire), the DFT at them; d_offset
+// (device, or null) receives them.
+int run_ofdm(amr_ofdm_plan* pl, const DemodIo& io, int8_t* soft, int64_t soft_stride, bool acquire = false,
+             int64_t* d_offset = nullptr) {
   if (int rc = check_demod_args(pl, io, ArgOrder::device)) return rc;
   core_clear_used(*pl);
   if (io.B == 0) return AMR_OK;
   const OfdmParams& p = pl->p;
   hipStream_t st = pl->stream;
   return timed(*pl, AMR_TO_LAUNCH, [&]() -> int {
+    if (acquire) {
+      if (int rc = run_acquire(pl, io.x, io.dtype, io.B, io.x_stride)) return rc;
+      if (d_offset)
+        HIP_TRY(hipMemcpyAsync(d_offset, pl->mem.off.get(), (size_t)io.B * 8, hipMemcpyDeviceToDevice, st));
+    }
     if (p.n_sym < 2) {                               // fewer than two symbols: b"", sync -1
       HIP_TRY(hipMemsetAsync(io.len, 0, (size_t)io.B * 8, st));
       HIP_TRY(hipMemsetAsync(io.sync, 0xFF, (size_t)io.B * 8, st));
@@ -102,8 +141,12 @@ int run_ofdm(amr_ofdm_plan* pl, const DemodIo& io, int8_t* soft, int64_t soft_st
     }
     double* Y = pl->mem.Y.as<double>();
     uint32_t* words = pl->mem.words.as<uint32_t>();
-    HIP_TRY_TIMED(*pl, AMR_TO_DFT,
-                  launch_ofdm_dft(io.x, io.dtype, io.x_stride, io.B, p, pl->mem.W.as<double>(), Y, st));
+    if (acquire)
+      HIP_TRY_TIMED(*pl, AMR_TO_DFT, launch_ofdm_dft_at(io.x, io.dtype, io.x_stride, io.B, p, pl->mem.W.as<double>(),
+                                                        pl->mem.off.as<int64_t>(), Y, st));
+    else
+      HIP_TRY_TIMED(*pl, AMR_TO_DFT,
+                    launch_ofdm_dft(io.x, io.dtype, io.x_stride, io.B, p, pl->mem.W.as<double>(), Y, st));
     HIP_TRY_TIMED(*pl, AMR_TO_SLICE, launch_ofdm_slice(Y, io.B, p, words, st));
     return timed(*pl, AMR_TO_SYNC_PACK, [&]() -> int {
       HIP_TRY(launch_sync_pack(words, p.n_words, p.n_bits, io.B, io.out, io.out_stride, io.len, io.sync, st));
@@ -122,8 +165,10 @@ int ofdm_host_staging(amr_ofdm_plan* pl) {
 }
 
 // a host entry (plan_core.h host_round_trip); soft: the soft values too,
-// through a staging block of this call's own
-int ofdm_demod_host(amr_ofdm_plan* plan, const char* who, const DemodIo& h, int8_t* soft, int64_t soft_stride) {
+// through a staging block of this call's own; acquire: as run_ofdm, the
+// offsets to `offset` (host, or null)
+int ofdm_demod_host(amr_ofdm_plan* plan, const char* who, const DemodIo& h, int8_t* soft, int64_t soft_stride,
+                    bool acquire = false, int64_t* offset = nullptr) {
   DevBuf d_soft;
   int64_t sv = 0;
   const int rc = host_round_trip(plan, who, h, Copy::sync, [&]() -> int {
@@ -138,7 +183,10 @@ int ofdm_demod_host(amr_ofdm_plan* plan, const char* who, const DemodIo& h, int8
       sv = std::max<int64_t>(plan->p.n_bits, 1);
       HIP_TRY(d_soft.reserve(h.B * sv, nullptr));
     }
-    return run_ofdm(plan, d, soft ? d_soft.as<int8_t>() : nullptr, sv);
+    if (int rc = run_ofdm(plan, d, soft ? d_soft.as<int8_t>() : nullptr, sv, acquire)) return rc;
+    if (acquire && offset)                     // queued like the round trip's own downloads, which wait for the stream
+      HIP_TRY(hipMemcpyAsync(offset, m.off.get(), (size_t)h.B * 8, hipMemcpyDeviceToHost, plan->stream));
+    return AMR_OK;
   });
   if (rc || !soft || h.B == 0) return rc;
   // only the values of the stream's bytes reach the caller's row
@@ -178,6 +226,51 @@ int ofdm_symbol_stages(const char* who, const double* Y, int64_t n_streams, int6
   if (words)
     HIP_TRY_ELSE(hipMemcpy(words, d_words.get(), (size_t)(n_streams * p.n_words) * 4, hipMemcpyDeviceToHost), bad);
   if (soft) HIP_TRY_ELSE(hipMemcpy(soft, d_soft.get(), (size_t)(n_streams * p.n_bits), hipMemcpyDeviceToHost), bad);
+  return AMR_OK;
+}
+
+// amr_ofdm_acquire_host / _device: the acquisition stage alone.  host: x, offset, dhat and E are host memory
+// (x staged in mem.d_x, the call waits); else device memory, the copies queued on the plan's stream.
+int ofdm_acquire_entry(amr_ofdm_plan* plan, const char* who, bool host, const void* x, int dtype, int64_t B,
+                       int64_t x_stride, int64_t* offset, int64_t* dhat, double* E) {
+  if (!plan || (B && (!x || !offset))) return fail(AMR_E_INVALID, std::string(who) + ": NULL argument");
+  std::lock_guard<std::mutex> lk(plan->mu);
+  const OfdmParams& p = plan->p;
+  const int64_t es = dtype_size(dtype), n = p.n;
+  if (es == 0) return fail(AMR_E_INVALID, "unknown dtype");
+  if (B < 0 || B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
+  if (x_stride < n) return fail(AMR_E_INVALID, "x_stride < n_samples");
+  HIP_TRY(hipSetDevice(plan->device));
+  core_clear_used(*plan);
+  if (B == 0) return AMR_OK;
+  amr_ofdm_plan::Mem& m = plan->mem;
+  hipStream_t st = plan->stream;
+  const void* d_x = x;
+  int64_t stride = x_stride;
+  if (host) {
+    HIP_TRY(m.d_x.reserve(std::max<int64_t>(plan->max_streams * n * 8, 8), st));
+    if (n > 0)
+      if (int rc = upload_batch(Copy::sync, m.d_x.get(), x, n * es, x_stride * es, B, st)) return rc;
+    d_x = m.d_x.get();
+    stride = n;
+  }
+  if (int rc = run_acquire(plan, d_x, dtype, B, stride)) return rc;
+  const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  HIP_TRY(hipMemcpyAsync(offset, m.off.get(), (size_t)B * 8, kind, st));
+  if (dhat) HIP_TRY(hipMemcpyAsync(dhat, m.dhat.get(), (size_t)B * 8, kind, st));
+  if (E) HIP_TRY(hipMemcpyAsync(E, m.E.get(), (size_t)(B * p.L) * 8, kind, st));
+  if (host) HIP_TRY(hipStreamSynchronize(st));
+  return AMR_OK;
+}
+
+// the checks amr_ofdm_demod_soft_* make before the shared contract, `soft` optional here
+int demod_acq_precheck(const amr_ofdm_plan* plan, const char* who, int64_t B, int64_t x_stride, int64_t out_stride,
+                       const int8_t* soft, int64_t soft_stride) {
+  const std::string name(who);
+  if (B < 0 || x_stride < 0 || out_stride < 0 || (soft && soft_stride < 0)) return fail(AMR_E_INVALID, name + ": negative argument");
+  if (!plan) return fail(AMR_E_INVALID, name + ": NULL argument");
+  if (soft && soft_stride < 8 * plan->out_cap)
+    return fail(AMR_E_INVALID, name + ": soft_stride < 8 * amr_ofdm_plan_out_capacity()");
   return AMR_OK;
 }
 
@@ -258,7 +351,14 @@ int64_t amr_ofdm_plan_scratch_bytes(const amr_ofdm_plan* plan) {
   if (!plan) return -1;
   const amr_ofdm_plan::Mem& m = plan->mem;
   return m.W.bytes() + m.Y.bytes() + m.words.bytes() + m.d_x.bytes() + m.d_out.bytes() + m.d_len.bytes() +
-         m.d_sync.bytes();
+         m.d_sync.bytes() + m.gq.bytes() + m.G.bytes() + m.E.bytes() + m.dhat.bytes() + m.off.bytes();
+}
+
+int64_t amr_ofdm_acquire_bytes_estimate(int64_t n_samples, int64_t sps, int K, int64_t max_streams) {
+  if (max_streams < 1) return fail(AMR_E_INVALID, "amr_ofdm_acquire_bytes_estimate: max_streams < 1");
+  OfdmParams p;
+  if (int rc = ofdm_params(n_samples, sps, K, 1, &p)) return rc;
+  return acq_bytes(p, max_streams);
 }
 
 int64_t amr_ofdm_plan_bytes_estimate(int64_t n_samples, int64_t sps, int K, int64_t max_streams) {
@@ -328,6 +428,69 @@ int amr_ofdm_symbols_host(amr_ofdm_plan* plan, const void* x, int dtype, int64_t
   HIP_TRY(hipMemcpyAsync(Y, plan->mem.Y.get(), (size_t)yb, hipMemcpyDeviceToHost, plan->stream));
   HIP_TRY(hipStreamSynchronize(plan->stream));
   return AMR_OK;
+}
+
+int amr_ofdm_symbols_at_host(amr_ofdm_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride,
+                             const int64_t* offset, double* Y) {
+  if (!plan || (B && (!x || !offset || !Y))) return fail(AMR_E_INVALID, "amr_ofdm_symbols_at_host: NULL argument");
+  std::lock_guard<std::mutex> lk(plan->mu);
+  const OfdmParams& p = plan->p;
+  const int64_t es = dtype_size(dtype), n = p.n;
+  if (es == 0) return fail(AMR_E_INVALID, "unknown dtype");
+  if (B < 0 || B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
+  if (x_stride < n) return fail(AMR_E_INVALID, "x_stride < n_samples");
+  for (int64_t i = 0; i < B; ++i)
+    if (offset[i] < -p.ncp || offset[i] > p.L - 1 - p.ncp)
+      return fail(AMR_E_INVALID, "amr_ofdm_symbols_at_host: offset outside [-Ncp, L - 1 - Ncp]");
+  HIP_TRY(hipSetDevice(plan->device));
+  const int64_t yb = B * p.n_sym * p.K * 16;
+  if (B == 0 || yb == 0) return AMR_OK;
+  DevBuf d_off;                                  // this call's own; the stream is drained before it goes
+  HIP_TRY(d_off.reserve(B * 8, nullptr));
+  HIP_TRY(plan->mem.d_x.reserve(std::max<int64_t>(plan->max_streams * n * 8, 8), plan->stream));
+  if (int rc = upload_batch(Copy::sync, plan->mem.d_x.get(), x, n * es, x_stride * es, B, plan->stream)) return rc;
+  HIP_TRY(hipMemcpy(d_off.get(), offset, (size_t)B * 8, hipMemcpyHostToDevice));
+  const hipError_t e = launch_ofdm_dft_at(plan->mem.d_x.get(), dtype, n, B, p, plan->mem.W.as<double>(),
+                                          d_off.as<int64_t>(), plan->mem.Y.as<double>(), plan->stream);
+  if (e == hipSuccess) (void)hipMemcpyAsync(Y, plan->mem.Y.get(), (size_t)yb, hipMemcpyDeviceToHost, plan->stream);
+  const hipError_t e2 = hipStreamSynchronize(plan->stream);
+  HIP_TRY(e);
+  HIP_TRY(e2);
+  return AMR_OK;
+}
+
+int amr_ofdm_acquire_host(amr_ofdm_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, int64_t* offset,
+                          int64_t* dhat, double* E) {
+  return ofdm_acquire_entry(plan, "amr_ofdm_acquire_host", true, x, dtype, B, x_stride, offset, dhat, E);
+}
+
+int amr_ofdm_acquire_device(amr_ofdm_plan* plan, const void* d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                            int64_t* d_offset, int64_t* d_dhat, double* d_E) {
+  return ofdm_acquire_entry(plan, "amr_ofdm_acquire_device", false, d_x, dtype, n_streams, x_stride, d_offset, d_dhat,
+                            d_E);
+}
+
+int amr_ofdm_demod_acq_host(amr_ofdm_plan* plan, const void* x, int dtype, int64_t B, int64_t x_stride, uint8_t* out,
+                            int64_t out_stride, int64_t* out_len, int64_t* sync_idx, int8_t* soft, int64_t soft_stride,
+                            int64_t* offset) {
+  if (int rc = demod_acq_precheck(plan, "amr_ofdm_demod_acq_host", B, x_stride, out_stride, soft, soft_stride))
+    return rc;
+  return ofdm_demod_host(plan, "amr_ofdm_demod_acq_host", {x, dtype, B, x_stride, out, out_stride, out_len, sync_idx},
+                         soft, soft_stride, true, offset);
+}
+
+int amr_ofdm_demod_acq_device(amr_ofdm_plan* plan, const void* d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                              uint8_t* d_out, int64_t out_stride, int64_t* d_out_len, int64_t* d_sync_idx,
+                              int8_t* d_soft, int64_t soft_stride, int64_t* d_offset) {
+  if (int rc = demod_acq_precheck(plan, "amr_ofdm_demod_acq_device", n_streams, x_stride, out_stride, d_soft,
+                                  soft_stride))
+    return rc;
+  if (n_streams && (!d_x || !d_out || !d_out_len || !d_sync_idx))
+    return fail(AMR_E_INVALID, "amr_ofdm_demod_acq_device: NULL argument");
+  std::lock_guard<std::mutex> lk(plan->mu);
+  HIP_TRY(hipSetDevice(plan->device));
+  return run_ofdm(plan, {d_x, dtype, n_streams, x_stride, d_out, out_stride, d_out_len, d_sync_idx}, d_soft,
+                  soft_stride, true, d_offset);
 }
 
 int amr_ofdm_slice_host(const double* Y, int64_t n_streams, int64_t n_sym, int K, uint32_t* words) {

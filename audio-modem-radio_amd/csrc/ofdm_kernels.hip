@@ -4,6 +4,7 @@
 // bit-equal to it, the transmit samples up to sin's last ulp.
 //
 //   k_ofdm_dft    Y[b][s][k] = sum_m x[b][s*L + Ncp + m] * W[k][m], the hot path
+//   k_ofdm_dft_at the same with each stream read from its own offset (§3k)
 //   k_ofdm_slice  the differential decision across time per subcarrier, packed
 //   k_ofdm_soft   two int8 per product (K4s's magnitudes and window rule)
 //   k_tx_ofdm_phase / k_tx_ofdm_synth   the modulator
@@ -43,10 +44,14 @@ __device__ __forceinline__ void dft_term(double (&pr)[G][4], double (&pi)[G][4],
   }
 }
 
-template <typename T, int G>
+// One group of subcarriers over the whole symbol, k_ofdm_dft's body.
+// AT (k_ofdm_dft_at): a row starts at its stream's offset, so
+// its tail may pass the stream's end: rowlim[r] is the count of the row's
+// samples below n, and a sample at or past it is staged as 0.0 without a load.
+template <typename T, int G, bool AT = false>
 __device__ __forceinline__ void dft_group(const T* __restrict__ x, const OfdmParams& p, CDouble* W, int k0,
                                           double (&tile)[kWave][kDftPitch], const int64_t (&rowbase)[kWave],
-                                          double* __restrict__ y) {
+                                          double* __restrict__ y, const int64_t (&rowlim)[kWave]) {
   const int lane = threadIdx.x;
   const int sj = lane & (kDftChunk - 1), sr = lane >> 5;   // staging: sample of the chunk, row parity
   double pr[G][4], pi[G][4];
@@ -63,13 +68,15 @@ __device__ __forceinline__ void dft_group(const T* __restrict__ x, const OfdmPar
 #pragma unroll
     for (int i = 0; i < kWave / 2; ++i) {
       const int64_t rb = rowbase[2 * i + sr];
-      raw[i] = x[rb >= 0 && sj < cnt ? rb + m0 + sj : safe];
+      if constexpr (AT) raw[i] = x[rb >= 0 && sj < cnt && m0 + sj < rowlim[2 * i + sr] ? rb + m0 + sj : safe];
+      else raw[i] = x[rb >= 0 && sj < cnt ? rb + m0 + sj : safe];
     }
     __syncthreads();                            // the previous chunk's reads are done
 #pragma unroll
     for (int i = 0; i < kWave / 2; ++i) {
       const int r = 2 * i + sr;
-      tile[r][sj] = rowbase[r] >= 0 && sj < cnt ? In<T>::cvt(raw[i]) : 0.0;
+      if constexpr (AT) tile[r][sj] = rowbase[r] >= 0 && sj < cnt && m0 + sj < rowlim[r] ? In<T>::cvt(raw[i]) : 0.0;
+      else tile[r][sj] = rowbase[r] >= 0 && sj < cnt ? In<T>::cvt(raw[i]) : 0.0;
     }
     __syncthreads();
     CDouble* w = W + (m0 * p.K + k0) * 2;
@@ -112,10 +119,58 @@ __global__ __launch_bounds__(kWave) void k_ofdm_dft(const T* __restrict__ x, int
   double* const y = live ? Y + (size_t)flat * (size_t)p.K * 2 : nullptr;
   for (int k0 = 0; k0 < p.K; k0 += kDftGroup) {
     const int g = p.K - k0;                     // wave-uniform
-    if (g >= 4) dft_group<T, 4>(x, p, W, k0, tile, rowbase, y);
-    else if (g == 3) dft_group<T, 3>(x, p, W, k0, tile, rowbase, y);
-    else if (g == 2) dft_group<T, 2>(x, p, W, k0, tile, rowbase, y);
-    else dft_group<T, 1>(x, p, W, k0, tile, rowbase, y);
+    if (g >= 4) dft_group<T, 4>(x, p, W, k0, tile, rowbase, y, rowbase);
+    else if (g == 3) dft_group<T, 3>(x, p, W, k0, tile, rowbase, y, rowbase);
+    else if (g == 2) dft_group<T, 2>(x, p, W, k0, tile, rowbase, y, rowbase);
+    else dft_group<T, 1>(x, p, W, k0, tile, rowbase, y, rowbase);
+  }
+}
+
+// k_ofdm_dft at per-stream offsets: symbol s of stream b starts at sample
+// offset[b] + s*L + Ncp of its row.  offset[b] >= -Ncp, so no row starts before
+// sample 0; offset[b] <= L - 1 - Ncp, so every row starts below S*L <= n (the
+// `safe` sample of lane 0 is always a real one) and only a stream's last
+// symbol can pass n: its samples from n on are zeros, never loads.  A wave
+// with no such row (all but about one in S / 64 of them, and none when the
+// offsets leave the tails whole) takes k_ofdm_dft's own staging loop: the
+// per-row limit costs a second LDS read and compare per load, and the staging
+// loop is what the kernel's time is.
+// rowbase and rowlim are written by one lane each and read by every lane with
+// no barrier in between, as k_ofdm_dft reads its rowbase: the workgroup is one
+// wave, and a wave's LDS operations complete in the order it issued them.
+template <typename T>
+__global__ __launch_bounds__(kWave) void k_ofdm_dft_at(const T* __restrict__ x, int64_t x_stride, int64_t n_streams,
+                                                       OfdmParams p, CDouble* W,
+                                                       const int64_t* __restrict__ offset, double* __restrict__ Y) {
+  __shared__ double tile[kWave][kDftPitch];
+  __shared__ int64_t rowbase[kWave];
+  __shared__ int64_t rowlim[kWave];
+  const int lane = threadIdx.x;
+  const int64_t S = p.n_sym;
+  const int64_t flat = (int64_t)blockIdx.x * kWave + lane;
+  const bool live = flat < n_streams * S;
+  {
+    const int64_t b = live ? flat / S : 0;
+    const int64_t s = flat - b * S;
+    const int64_t i0 = live ? offset[b] + s * p.L + p.ncp : 0;   // 0 <= i0 < S*L
+    rowbase[lane] = live ? b * x_stride + i0 : -1;
+    rowlim[lane] = p.n - i0;
+  }
+  const bool cut = __any(live && rowlim[lane] < p.nu) != 0;   // wave-uniform: the workgroup is one wave
+  double* const y = live ? Y + (size_t)flat * (size_t)p.K * 2 : nullptr;
+  for (int k0 = 0; k0 < p.K; k0 += kDftGroup) {
+    const int g = p.K - k0;                     // wave-uniform
+    if (cut) {
+      if (g >= 4) dft_group<T, 4, true>(x, p, W, k0, tile, rowbase, y, rowlim);
+      else if (g == 3) dft_group<T, 3, true>(x, p, W, k0, tile, rowbase, y, rowlim);
+      else if (g == 2) dft_group<T, 2, true>(x, p, W, k0, tile, rowbase, y, rowlim);
+      else dft_group<T, 1, true>(x, p, W, k0, tile, rowbase, y, rowlim);
+    } else {
+      if (g >= 4) dft_group<T, 4>(x, p, W, k0, tile, rowbase, y, rowbase);
+      else if (g == 3) dft_group<T, 3>(x, p, W, k0, tile, rowbase, y, rowbase);
+      else if (g == 2) dft_group<T, 2>(x, p, W, k0, tile, rowbase, y, rowbase);
+      else dft_group<T, 1>(x, p, W, k0, tile, rowbase, y, rowbase);
+    }
   }
 }
 
@@ -394,6 +449,26 @@ hipError_t launch_ofdm_dft(const void* x, int dtype, int64_t x_stride, int64_t n
   else if (dtype == kI16)
     hipLaunchKernelGGL(k_ofdm_dft<int16_t>, grid, dim3(kWave), 0, st, (const int16_t*)x, x_stride, n_streams, p, w,
                        Y);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_ofdm_dft_at(const void* x, int dtype, int64_t x_stride, int64_t n_streams, const OfdmParams& p,
+                              const double* W, const int64_t* offset, double* Y, hipStream_t st) {
+  const int64_t total = n_streams * p.n_sym;
+  if (total < 1) return hipSuccess;
+  const dim3 grid((unsigned)((total + kWave - 1) / kWave));
+  CDouble* w = (CDouble*)W;
+  if (dtype == kF32)
+    hipLaunchKernelGGL(k_ofdm_dft_at<float>, grid, dim3(kWave), 0, st, (const float*)x, x_stride, n_streams, p, w,
+                       offset, Y);
+  else if (dtype == kF64)
+    hipLaunchKernelGGL(k_ofdm_dft_at<double>, grid, dim3(kWave), 0, st, (const double*)x, x_stride, n_streams, p, w,
+                       offset, Y);
+  else if (dtype == kI16)
+    hipLaunchKernelGGL(k_ofdm_dft_at<int16_t>, grid, dim3(kWave), 0, st, (const int16_t*)x, x_stride, n_streams, p,
+                       w, offset, Y);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

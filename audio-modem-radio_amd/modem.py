@@ -20,6 +20,10 @@ PSK modem, 3 bits per symbol, beside the psk8_* aliases the reference keeps:
 ofdm (no reference counterpart): a real multi-carrier DQPSK
 modem beside the ofdm_*_simple aliases the reference keeps:
   ofdm_modulate, ofdm_demodulate (+ _batch, _soft, _soft_batch).
+  A capture that does not start on a symbol boundary:
+  ofdm_acquire (+ _batch) finds the boundary from the cyclic prefix, and the
+  demodulators' acquire=True reads every stream from its own (a symbol of
+  fewer than 8 samples has no prefix: nothing is acquired, the offset is 0).
 
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
@@ -217,7 +221,7 @@ def _ofdm_input(samples) -> np.ndarray:
     return x if x.dtype in _amr.DTYPES else x.astype(np.float64)
 
 
-def _ofdm_batch(x2d, baud, carrier, num_subcarriers, samp_rate, soft=False):
+def _ofdm_batch(x2d, baud, carrier, num_subcarriers, samp_rate, soft=False, acquire=False):
     x2d = _ofdm_input(x2d)
     if x2d.ndim != 2:
         raise ValueError("batch input must be a 2-D [streams, samples] array")
@@ -225,38 +229,64 @@ def _ofdm_batch(x2d, baud, carrier, num_subcarriers, samp_rate, soft=False):
     _amr.ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)      # ValueError, also for an empty batch
     if B == 0:
         return ([], []) if soft else []
-    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B)
+    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B, acquire=acquire)
     if soft:
-        outs, _, softs = plan.demod_soft_host(x2d)
+        outs, _, softs = plan.demod_soft_host(x2d, acquire=acquire)[:3]
         return outs, softs
-    return plan.demod_host(x2d)[0]
+    return plan.demod_host(x2d, acquire=acquire)[0]
 
 
-def ofdm_demodulate(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> bytes:
-    """Multi-carrier DQPSK demodulation of one stream, on the GPU."""
+def ofdm_demodulate(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False) -> bytes:
+    """Multi-carrier DQPSK demodulation of one stream, on the GPU.  acquire=True: the
+    capture need not start on a symbol boundary (ofdm_acquire's offset is applied)."""
     x = _ofdm_input(samples)
     if x.ndim != 1:
         raise ValueError("ofdm_demodulate expects a 1-D sample array (use ofdm_demodulate_batch)")
-    return _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate)[0]
+    return _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, acquire=acquire)[0]
 
 
-def ofdm_demodulate_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> list:
+def ofdm_demodulate_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False) -> list:
     """[B, N] equal-length streams -> B bytes objects (each == ofdm_demodulate(row))."""
-    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate)
+    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, acquire=acquire)
 
 
-def ofdm_demodulate_soft(samples, baud, carrier, num_subcarriers, samp_rate=96000):
+def ofdm_demodulate_soft(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False):
     """ofdm_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
     x = _ofdm_input(samples)
     if x.ndim != 1:
         raise ValueError("ofdm_demodulate_soft expects a 1-D sample array (use ofdm_demodulate_soft_batch)")
-    outs, softs = _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, soft=True)
+    outs, softs = _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
     return outs[0], softs[0]
 
 
-def ofdm_demodulate_soft_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000):
+def ofdm_demodulate_soft_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False):
     """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
-    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, soft=True)
+    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
+
+
+def ofdm_acquire_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> np.ndarray:
+    """[B, N] equal-length streams -> int64 [B]: the sample offset o of each stream at which
+    its OFDM symbols are read, in [-Ncp, L - 1 - Ncp]: the cyclic prefix's
+    estimated start less half a prefix.  An aligned capture gives -(Ncp // 2).
+    A symbol of fewer than 8 samples has no prefix (Ncp = L // 8 = 0): the offset is
+    then 0 whatever the capture, and acquire=True decodes as acquire=False does."""
+    x2d = _ofdm_input(samples)
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    B, n = x2d.shape
+    _amr.ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)
+    if B == 0:
+        return np.zeros(0, np.int64)
+    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B, acquire=True)
+    return plan.acquire(x2d)[0]
+
+
+def ofdm_acquire(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> int:
+    """ofdm_acquire_batch of one stream."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("ofdm_acquire expects a 1-D sample array (use ofdm_acquire_batch)")
+    return int(ofdm_acquire_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate)[0])
 
 
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:

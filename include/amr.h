@@ -807,7 +807,8 @@ typedef struct amr_ofdm_plan amr_ofdm_plan;
 #define AMR_TO_SLICE 1        /* k_ofdm_slice */
 #define AMR_TO_SYNC_PACK 2    /* sync search and byte pack; in a soft call k_ofdm_soft too (it reads their window) */
 #define AMR_TO_LAUNCH 3       /* the whole launch */
-#define AMR_TO_COUNT 4
+#define AMR_TO_ACQUIRE 4      /* k_ofdm_fold and k_ofdm_acq_min of an acquiring call (inside AMR_TO_LAUNCH) */
+#define AMR_TO_COUNT 5
 int amr_ofdm_plan_create(amr_ofdm_plan **plan, int device, int64_t n_samples, int64_t sps, int K,
                          const int32_t *bins, const double *W, int64_t max_streams);
 int amr_ofdm_plan_destroy(amr_ofdm_plan *plan);
@@ -837,6 +838,44 @@ int amr_ofdm_demod_soft_device(amr_ofdm_plan *plan, const void *d_x, int dtype, 
 /* the DFT stage alone: Y [n_streams][S][K][2] float64 (re, im) */
 int amr_ofdm_symbols_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
                           double *Y);
+/* ---- ofdm acquisition: the symbol boundary of an unaligned capture (DESIGN.md
+ * §3k, tests/ofdm_acquire_cases.py).  Float64, no fma, samples read as the
+ * receiver reads them; per stream of n samples, with Q = 64:
+ *   M = (n - Nu) / L if n >= Nu + L, else 0
+ *   g_q[r] = sum over s = 64 q .. min(64 q + 64, M) - 1 of d * d,
+ *            d = x[s L + r] - x[s L + r + Nu],   sequential in s from 0.0
+ *   G[r]  = g_0[r] + g_1[r] + ...                sequential in q from 0.0
+ *   E[d]  = sum over i = 0 .. Ncp - 1 of G[(d + i) % L], sequential in i from 0.0
+ *   dhat  = best after: best = 0; for d = 1 .. L - 1: if (E[d] < E[best]) best = d
+ *   o     = dhat - Ncp / 2;  if (o > L - 1 - Ncp) o -= L      in [-Ncp, L - 1 - Ncp]
+ * The acquired demodulation of x is the demodulation above of shift(x, o):
+ * shift(x, o)[i] = x[i + o] where 0 <= i + o < n, else 0.0, the length n kept;
+ * S, the bit count, the output capacity and the sync search are unchanged.
+ * L < 8 has no prefix (Ncp = 0): E is zeros, o = 0, nothing is acquired.
+ * The work buffers are allocated on the plan's first acquiring call (then part
+ * of amr_ofdm_plan_scratch_bytes); amr_ofdm_acquire_bytes_estimate is their
+ * size by host arithmetic (< 0: bad shape). */
+int64_t amr_ofdm_acquire_bytes_estimate(int64_t n_samples, int64_t sps, int K, int64_t max_streams);
+/* the acquisition stage alone: offset [n_streams] (o), dhat [n_streams] and E
+ * [n_streams][L]; dhat and E may be NULL.  _device: device pointers, queued on
+ * the plan's stream. */
+int amr_ofdm_acquire_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                          int64_t *offset, int64_t *dhat, double *E);
+int amr_ofdm_acquire_device(amr_ofdm_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                            int64_t *d_offset, int64_t *d_dhat, double *d_E);
+/* the DFT stage at given offsets: Y of shift(x[b], offset[b]); an offset outside
+ * [-Ncp, L - 1 - Ncp] is AMR_E_INVALID before any device work */
+int amr_ofdm_symbols_at_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                             const int64_t *offset, double *Y);
+/* amr_ofdm_demod_soft_* with the acquisition in front, all on the plan's stream
+ * with no host round trip in between; the offsets to offset [n_streams].  soft
+ * and offset may be NULL (soft_stride is then ignored). */
+int amr_ofdm_demod_acq_host(amr_ofdm_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                            uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx, int8_t *soft,
+                            int64_t soft_stride, int64_t *offset);
+int amr_ofdm_demod_acq_device(amr_ofdm_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                              uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                              int8_t *d_soft, int64_t soft_stride, int64_t *d_offset);
 /* the slicer and soft stages alone on given Y [n_streams][n_sym][K][2]: words
  * [n_streams][max(1, ceil(2 K (n_sym - 1) / 32))] (MSB first), soft
  * [n_streams][2 K (n_sym - 1)] (every bit from 0) */
