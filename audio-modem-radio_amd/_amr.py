@@ -80,10 +80,20 @@ EXPORTS = [
     "amr_ofdm_demod_soft_device", "amr_ofdm_symbols_host", "amr_ofdm_slice_host", "amr_ofdm_soft_host",
     "amr_ofdm_modulate_host", "amr_ofdm_acquire_bytes_estimate", "amr_ofdm_acquire_host", "amr_ofdm_acquire_device",
     "amr_ofdm_symbols_at_host", "amr_ofdm_demod_acq_host", "amr_ofdm_demod_acq_device",
+    "amr_dsss_plan_create", "amr_dsss_plan_destroy", "amr_dsss_plan_synchronize", "amr_dsss_plan_enable_timing",
+    "amr_dsss_plan_timings", "amr_dsss_plan_out_capacity", "amr_dsss_plan_scratch_bytes",
+    "amr_dsss_plan_bytes_estimate", "amr_dsss_acquire_bytes_estimate", "amr_dsss_demod_host", "amr_dsss_demod_device",
+    "amr_dsss_acquire_host", "amr_dsss_acquire_device", "amr_dsss_symbols_at_host", "amr_dsss_slice_host",
+    "amr_dsss_soft_host", "amr_dsss_modulate_host",
 ]
 TO_NAMES = ["dft", "slice", "sync_pack", "launch"]
 TO_SLOTS = TO_NAMES + ["acquire"]                  # AMR_TO_*: "acquire" is run by an acquiring call only
 OFDM_MAX_K = 64
+TD_SLOTS = ["despread", "slice", "sync_pack", "launch", "acquire"]   # AMR_TD_*: "acquire" on acquiring calls only
+DSSS_MAX_C = 64
+# spread's default code, 0x8B63: balanced, no cyclic run longer than 3, every off-peak
+# even and odd periodic autocorrelation within 4 of 16
+DSSS_CODE = [1, 0, 0, 0, 1, 0, 1, 1, 0, 1, 1, 0, 0, 0, 1, 1]
 
 TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK = 0, 1, 2, 3, 4
 TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL, "d8psk": TX_D8PSK}
@@ -466,6 +476,23 @@ def lib():
             "amr_ofdm_symbols_at_host": (I32, [P, P, I32, I64, I64, P, P]),
             "amr_ofdm_demod_acq_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P]),
             "amr_ofdm_demod_acq_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P]),
+            "amr_dsss_plan_create": (I32, [P, I32, I64, I64, I32, I64, P, P, P, I64]),
+            "amr_dsss_plan_destroy": (I32, [P]),
+            "amr_dsss_plan_synchronize": (I32, [P]),
+            "amr_dsss_plan_enable_timing": (I32, [P, I32]),
+            "amr_dsss_plan_timings": (I32, [P, P, I32]),
+            "amr_dsss_plan_out_capacity": (I64, [P]),
+            "amr_dsss_plan_scratch_bytes": (I64, [P]),
+            "amr_dsss_plan_bytes_estimate": (I64, [I64, I64, I32, I64]),
+            "amr_dsss_acquire_bytes_estimate": (I64, [I64, I64, I32, I64]),
+            "amr_dsss_demod_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, I32]),
+            "amr_dsss_demod_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, I32]),
+            "amr_dsss_acquire_host": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_dsss_acquire_device": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_dsss_symbols_at_host": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_dsss_slice_host": (I32, [P, I64, I64, P]),
+            "amr_dsss_soft_host": (I32, [P, I64, I64, P]),
+            "amr_dsss_modulate_host": (I32, [I64, I32, I64, P, P, P, I64, P, I64, P, I64, I64, P, I64]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1200,6 +1227,217 @@ def ofdm_soft(Y: np.ndarray) -> np.ndarray:
     B, S, K = Y.shape
     soft = np.zeros((B, max(0, 2 * K * (S - 1))), np.int8)
     check(lib().amr_ofdm_soft_host(ptr(Y), B, S, K, ptr(soft)))
+    return soft
+
+
+# ---------------------------------------------------------------------------
+# spread: the direct-sequence DBPSK modem (tests/spread_cases.py)
+def _dsss_code(code) -> np.ndarray:
+    c = np.asarray(DSSS_CODE if code is None else code)
+    if c.ndim != 1 or not 2 <= c.size <= DSSS_MAX_C:
+        raise ValueError(f"spread: a code of {c.size if c.ndim == 1 else c.shape} chips, outside [2, {DSSS_MAX_C}]")
+    if not np.all((c == 0) | (c == 1)):
+        raise ValueError("spread: every code entry must be 0 or 1")
+    return c.astype(np.int64)
+
+
+def dsss_geometry(baud, carrier, code=None, samp_rate=96000):
+    """(spc, L, cyc, code int64 [C]) of DESIGN.md §3l, or ValueError when the
+    geometry is not valid (host arithmetic, before any device work).  baud is the chip rate."""
+    c = _dsss_code(code)
+    spc = int(samp_rate / baud)
+    if spc < 1:
+        raise ValueError("spread: fewer than one sample per chip")
+    L = c.size * spc
+    if L > 1 << 24:
+        raise ValueError(f"spread: {L} samples per bit, more than 2^24")
+    cyc = int(np.floor(float(carrier) * L / float(samp_rate) + 0.5))
+    if cyc < 1:
+        raise ValueError("spread: less than one carrier cycle per bit")
+    if 2 * cyc >= L:
+        raise ValueError(f"spread: {cyc} carrier cycles in a bit of {L} samples, at or above half the sample rate")
+    return spc, L, cyc, c
+
+
+def design_dsss(baud, carrier, code=None, samp_rate=96000):
+    """The geometry and the tables over i = 0 .. L-1, th = (2 pi) * (((cyc * i) % L) / L):
+    Wc [L][2] = (cos th, -sin th), T [L][2] = sg * Wc, Sn [L] = sin th, cs [C] = 1.0 - 2.0 * code;
+    what the plan and the modulator take, and what tests/spread_cases.py correlates against."""
+    spc, L, cyc, c = dsss_geometry(baud, carrier, code, samp_rate)
+    i = np.arange(L, dtype=np.int64)
+    th = (2 * np.pi) * (((cyc * i) % L) / L)
+    Wc = np.ascontiguousarray(np.stack([np.cos(th), -np.sin(th)], axis=-1), np.float64)
+    Sn = np.ascontiguousarray(np.sin(th), np.float64)
+    cs = 1.0 - 2.0 * c.astype(np.float64)
+    sg = cs[i // spc]
+    T = np.ascontiguousarray(sg[:, None] * Wc, np.float64)
+    return spc, L, cyc, c, Wc, T, Sn, cs
+
+
+class DsssPlan:
+    """A device plan of the spread demodulator: the tables in HBM + Y and the bit words for max_streams streams."""
+
+    def __init__(self, n: int, baud, carrier, code=None, samp_rate=96000, max_streams=64, device=None):
+        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
+        self.spc, self.L, self.cyc, self.code, Wc, T, _, cs = design_dsss(baud, carrier, code, samp_rate)
+        self.C = int(self.code.size)
+        self.S = self.n // self.L
+        require_gpu()
+        self.device = default_device() if device is None else device
+        self.max_streams = int(max_streams)
+        h = ctypes.c_void_p()
+        check(lib().amr_dsss_plan_create(ctypes.byref(h), self.device, self.n, self.spc, self.C, self.cyc, ptr(Wc),
+                                         ptr(T), ptr(cs), self.max_streams))
+        self.handle = h
+        self.out_cap = int(lib().amr_dsss_plan_out_capacity(h))
+        self.lock = threading.Lock()
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and _lib is not None:
+            try:
+                _lib.amr_dsss_plan_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _batches(self, x):
+        x, stride = _rows(x)
+        for s0 in range(0, x.shape[0], self.max_streams):
+            yield s0, x[s0:s0 + self.max_streams], stride
+
+    def demod_host(self, x: np.ndarray, soft=False, acquire=True):
+        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync,
+        list[int8 array] or None, offsets int64 [B]); acquire: each stream from its own acquired offset."""
+        outs, softs = [], []
+        syncs, offs = np.empty(x.shape[0], np.int64), np.empty(x.shape[0], np.int64)
+        cap = max(self.out_cap, 1)
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            sv = np.empty((nb, 8 * cap), np.int8) if soft else None
+            ln, sy, of = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty(nb, np.int64)
+            with self.lock:
+                check(lib().amr_dsss_demod_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
+                                                ptr(ln), ptr(sy), ptr(sv) if soft else None, 8 * cap, ptr(of),
+                                                1 if acquire else 0))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            if soft:
+                softs += [sv[i, :8 * ln[i]].copy() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+            offs[s0:s0 + nb] = of
+        return outs, syncs, (softs if soft else None), offs
+
+    def acquire(self, x: np.ndarray):
+        """The acquisition stage alone (amr_dsss_acquire_host): (offset int64 [B], P float64 [B][L])."""
+        B = x.shape[0]
+        off, P = np.empty(B, np.int64), np.empty((B, self.L))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            of, pb = np.empty(nb, np.int64), np.empty((nb, self.L))
+            with self.lock:
+                check(lib().amr_dsss_acquire_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(of),
+                                                  ptr(pb)))
+            off[s0:s0 + nb], P[s0:s0 + nb] = of, pb
+        return off, P
+
+    def symbols_at(self, x: np.ndarray, offsets=None) -> np.ndarray:
+        """The despreader alone at given per-stream offsets, default zeros (amr_dsss_symbols_at_host):
+        Y [B][S] complex128."""
+        offsets = np.zeros(x.shape[0], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64)
+        Y = np.zeros((x.shape[0], self.S, 2))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            yb = np.zeros((nb, self.S, 2))
+            ob = np.ascontiguousarray(offsets[s0:s0 + nb])
+            with self.lock:
+                check(lib().amr_dsss_symbols_at_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(ob),
+                                                     ptr(yb)))
+            Y[s0:s0 + nb] = yb
+        return Y.view(np.complex128)[..., 0]
+
+    def scratch_bytes(self) -> int:
+        """Device bytes this plan holds (tables, Y, words + host-API staging + the acquisition buffers once used)."""
+        return int(lib().amr_dsss_plan_scratch_bytes(self.handle)) if self.handle else 0
+
+    def enable_timing(self, on=True):
+        check(lib().amr_dsss_plan_enable_timing(self.handle, 1 if on else 0))
+
+    def synchronize(self):
+        check(lib().amr_dsss_plan_synchronize(self.handle))
+
+    def timings(self) -> dict:
+        ms = (ctypes.c_float * len(TD_SLOTS))()
+        check(lib().amr_dsss_plan_timings(self.handle, ms, len(TD_SLOTS)))
+        return {k: float(v) for k, v in zip(TD_SLOTS, ms) if v >= 0}
+
+
+def get_dsss_plan(n: int, baud, carrier, code, samp_rate, batch: int, acquire=False) -> DsssPlan:
+    """The shared plan cache, keyed by the call's parameters, the code among them (and device).  acquire: the
+    plan is about to acquire; the first time, the cache makes room for its acquisition buffers."""
+    dev = default_device()
+    spc, L, cyc, c = dsss_geometry(baud, carrier, code, samp_rate)      # ValueError before any plan is evicted
+    C = int(c.size)
+    key = ("dsss", int(n), float(baud), float(carrier), tuple(int(v) for v in c), float(samp_rate), dev)
+    need = stream_bucket(batch, PSK_MAX_CHUNK)
+
+    def estimate(m):
+        return max(0, int(lib().amr_dsss_plan_bytes_estimate(int(n), spc, C, m)))
+    pl = plan_cache.get(key, need, lambda m: DsssPlan(n, baud, carrier, c, samp_rate, max_streams=m, device=dev),
+                        estimate)
+    if acquire and not getattr(pl, "acquires", False):
+        plan_cache.reserve(key, max(0, int(lib().amr_dsss_acquire_bytes_estimate(int(n), spc, C, pl.max_streams))))
+        pl.acquires = True
+    return pl
+
+
+def dsss_tx_samples(n_bytes: int, baud, carrier, code=None, samp_rate=96000) -> int:
+    """len() of spread_modulate's output for an n_bytes payload: (81 + 8 n) * L."""
+    return (81 + 8 * int(n_bytes)) * dsss_geometry(baud, carrier, code, samp_rate)[1]
+
+
+def dsss_modulate(datas, baud, carrier, code=None, samp_rate=96000, n_out=None, pcm=False):
+    """Batched spread modulator on the GPU (amr_dsss_modulate_host): [B][n_out]
+    float32, cut / zero-padded to n_out (default: the longest natural length);
+    pcm=True also returns wav_from_array's int16."""
+    spc, L, cyc, c, _, _, Sn, cs = design_dsss(baud, carrier, code, samp_rate)   # the geometry's ValueError
+    n = len(datas)
+    lens = np.array([len(d) for d in datas], np.int64)
+    require_gpu()
+    if n_out is None:
+        n_out = max(((81 + 8 * int(v)) * L for v in lens), default=0)
+    stride = max(1, int(lens.max()) if n else 1)
+    buf = np.zeros((max(n, 1), stride), np.uint8)
+    for i, d in enumerate(datas):
+        buf[i, :len(d)] = np.frombuffer(bytes(d), np.uint8)
+    out = np.zeros((n, n_out), np.float32)
+    pc = np.zeros((n, n_out), np.int16) if pcm else None
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_dsss_modulate_host(spc, int(c.size), cyc, ptr(cs), ptr(Sn), ptr(buf), stride, ptr(lens), n,
+                                       ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out))
+    return (out, pc) if pcm else out
+
+
+def dsss_slice(Y: np.ndarray) -> np.ndarray:
+    """The slicer stage alone on the GPU (k_dsss_slice): Y [B][S] complex128 -> the decided bits [B][S - 1] as uint8."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S = Y.shape
+    nbits = max(0, S - 1)
+    words = np.zeros((B, max(1, (nbits + 31) // 32)), np.uint32)
+    check(lib().amr_dsss_slice_host(ptr(Y), B, S, ptr(words)))
+    bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
+    return bits[:, :nbits]
+
+
+def dsss_soft(Y: np.ndarray) -> np.ndarray:
+    """The soft stage alone on the GPU (k_dsss_slice then k_dsss_soft): Y [B][S]
+    complex128 -> int8 [B][S - 1], one value per decided bit from bit 0."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S = Y.shape
+    soft = np.zeros((B, max(0, S - 1)), np.int8)
+    check(lib().amr_dsss_soft_host(ptr(Y), B, S, ptr(soft)))
     return soft
 
 

@@ -25,6 +25,12 @@ modem beside the ofdm_*_simple aliases the reference keeps:
   demodulators' acquire=True reads every stream from its own (a symbol of
   fewer than 8 samples has no prefix: nothing is acquired, the offset is 0).
 
+spread (no reference counterpart): a real direct-sequence
+DBPSK modem beside the dsss_modulate alias the reference keeps (a BPSK call):
+  spread_modulate, spread_demodulate (+ _batch, _soft, _soft_batch), which
+  acquire the code phase of a capture that starts anywhere by default, and
+  spread_acquire (+ _batch), the acquisition alone.
+
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
@@ -289,6 +295,77 @@ def ofdm_acquire(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> in
     return int(ofdm_acquire_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate)[0])
 
 
+# ---------------------------------------------------------------------------
+# spread: direct-sequence DBPSK.  `baud` is the chip rate; one
+# bit is a repetition of the code, despread by one FP64 correlation and decided
+# differentially.  A capture may start anywhere: acquisition (the default)
+# finds the code phase by a sliding code correlation over every sample offset
+# of a bit.  Samples as ofdm reads them.
+def _spread_batch(x2d, baud, carrier, code, samp_rate, soft=False, acquire=True):
+    x2d = _ofdm_input(x2d)
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    B, n = x2d.shape
+    _amr.dsss_geometry(baud, carrier, code, samp_rate)                 # ValueError, also for an empty batch
+    if B == 0:
+        return ([], []) if soft else []
+    plan = _amr.get_dsss_plan(n, baud, carrier, code, samp_rate, B, acquire=acquire)
+    outs, _, softs, _ = plan.demod_host(x2d, soft=soft, acquire=acquire)
+    return (outs, softs) if soft else outs
+
+
+def spread_demodulate(samples, baud, carrier, code=None, samp_rate=96000, acquire=True) -> bytes:
+    """Direct-sequence DBPSK demodulation of one stream, on the GPU.  acquire=False: the capture
+    starts on a bit boundary (offset 0); the default finds the boundary first (spread_acquire)."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("spread_demodulate expects a 1-D sample array (use spread_demodulate_batch)")
+    return _spread_batch(x[None, :], baud, carrier, code, samp_rate, acquire=acquire)[0]
+
+
+def spread_demodulate_batch(samples, baud, carrier, code=None, samp_rate=96000, acquire=True) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == spread_demodulate(row))."""
+    return _spread_batch(samples, baud, carrier, code, samp_rate, acquire=acquire)
+
+
+def spread_demodulate_soft(samples, baud, carrier, code=None, samp_rate=96000, acquire=True):
+    """spread_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("spread_demodulate_soft expects a 1-D sample array (use spread_demodulate_soft_batch)")
+    outs, softs = _spread_batch(x[None, :], baud, carrier, code, samp_rate, soft=True, acquire=acquire)
+    return outs[0], softs[0]
+
+
+def spread_demodulate_soft_batch(samples, baud, carrier, code=None, samp_rate=96000, acquire=True):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _spread_batch(samples, baud, carrier, code, samp_rate, soft=True, acquire=acquire)
+
+
+def spread_acquire_batch(samples, baud, carrier, code=None, samp_rate=96000) -> np.ndarray:
+    """[B, N] equal-length streams -> int64 [B]: the sample offset in [0, L - 1] at which each
+    stream's bits begin: the first maximum over the offsets of a bit of the
+    despread energy summed over the capture.  A bit boundary only: which bit is which is the
+    sync word's business."""
+    x2d = _ofdm_input(samples)
+    if x2d.ndim != 2:
+        raise ValueError("batch input must be a 2-D [streams, samples] array")
+    B, n = x2d.shape
+    _amr.dsss_geometry(baud, carrier, code, samp_rate)
+    if B == 0:
+        return np.zeros(0, np.int64)
+    plan = _amr.get_dsss_plan(n, baud, carrier, code, samp_rate, B, acquire=True)
+    return plan.acquire(x2d)[0]
+
+
+def spread_acquire(samples, baud, carrier, code=None, samp_rate=96000) -> int:
+    """spread_acquire_batch of one stream."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError("spread_acquire expects a 1-D sample array (use spread_acquire_batch)")
+    return int(spread_acquire_batch(x[None, :], baud, carrier, code, samp_rate)[0])
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):
@@ -466,15 +543,27 @@ def ofdm_modulate(data_bytes: bytes, baud, carrier, num_subcarriers, samp_rate=9
     return _amr.ofdm_modulate([bytes(data_bytes)], baud, carrier, num_subcarriers, samp_rate)[0]
 
 
+def spread_modulate(data_bytes: bytes, baud, carrier, code=None, samp_rate=96000) -> np.ndarray:
+    """Direct-sequence DBPSK: [1,0]*40 + the payload's bits, one bit per
+    repetition of `code` (default _amr.DSSS_CODE, 16 chips) at `baud` chips per second, a 1 as a
+    sign change from the bit before; a bit holds a whole number of carrier cycles, so the
+    carrier is continuous.  (81 + 8 len) * C * spc samples."""
+    return _amr.dsss_modulate([bytes(data_bytes)], baud, carrier, code, samp_rate)[0]
+
+
 def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False,
-                   num_subcarriers=None):
+                   num_subcarriers=None, code=None):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
     cut / zero-padded to n_out; default the longest), plus wav_from_array's
     int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' | 'd8psk' (f0 = carrier) or
     'fsk' (f0 = mark_freq, f1 = space_freq), or 'hell' (datas: texts or UTF-8
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
     pass baud=122.5 for the reference's default), or 'ofdm' (f0 = carrier,
-    num_subcarriers required)."""
+    num_subcarriers required), or 'spread' (f0 = carrier, baud = the chip rate,
+    code: the chips, default _amr.DSSS_CODE)."""
+    if kind == "spread":
+        return _amr.dsss_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, code, samp_rate,
+                                  n_out, pcm)
     if kind == "ofdm":
         if num_subcarriers is None:
             raise ValueError("modulate_batch('ofdm', ...) needs num_subcarriers")

@@ -95,7 +95,8 @@ extern "C" {
                                   the 8-ary differential PSK modem: AMR_PSK_D8PSK (a plan kind,
                                   and a kind of amr_psk_slice_host / amr_psk_soft_host) and
                                   AMR_TX_D8PSK (a modulation mode); the multi-carrier DQPSK
-                                  modem (amr_ofdm_*, AMR_TO_*) */
+                                  modem (amr_ofdm_*, AMR_TO_*); the direct-sequence DBPSK
+                                  modem (amr_dsss_*, AMR_TD_*) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -890,6 +891,95 @@ int amr_ofdm_soft_host(const double *Y, int64_t n_streams, int64_t n_sym, int K,
  *   float32((sum_k sin((2 pi) * (((bins[k]*m) % Nu) / Nu) + ph[s][k])) * (1.0 / K))
  * the sum sequential in k from 0.0.  out / pcm / n_out as amr_modulate_host. */
 int amr_ofdm_modulate_host(double baud, double carrier, double sample_rate, int K, const uint8_t *data,
+                           int64_t data_stride, const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride,
+                           int64_t n_out, int16_t *pcm, int64_t pcm_stride);
+
+/* ---- spread: a direct-sequence DBPSK modem with code acquisition (no
+ * reference counterpart: the reference's dsss_modulate calls BPSK and it has
+ * no dsss_demodulate; DESIGN.md §3l, tests/spread_cases.py) ---------------------
+ * Geometry for (spc, C, cyc): spc samples per chip, C chips per bit, one bit is
+ * L = C * spc samples and holds cyc whole carrier cycles.  Valid iff
+ * 2 <= C <= 64, spc >= 1, cyc >= 1, 2 * cyc < L and L <= 2^24; anything else is
+ * AMR_E_INVALID before any device work.
+ * Tables (the caller's, float64), over i = 0 .. L-1 with th = (2 pi) *
+ * (((cyc * i) % L) / L) and sg[i] = cs[i / spc]:  Wc [L][2] = (cos th, -sin th),
+ * T [L][2] = sg[i] * Wc[i], Sn [L] = sin th; cs [C] the chip signs, +1.0 for a
+ * code bit 0 and -1.0 for a 1.
+ * Receiver at offset o in [0, L-1] (0 when not acquired): x' = shift(x, o),
+ * shift(x, o)[i] = x[i + o] while i + o < n, else 0.0; S = n_samples / L,
+ *   Y[s] = sum_i x'[s*L + i] * T[i]        in four interleaved partial sums
+ * p[i & 3], each sequential in i from 0.0, every product rounded before it is
+ * added (no fma), combined as (p0 + p1) + (p2 + p3) per component;
+ * d = Y[s+1] * conj(Y[s]) (numpy's multiply, as the PSK slicers); the bit is
+ * 1 iff dr < 0 (NaN and zeros give 0): S - 1 bits per stream, sync search and
+ * byte pack as for the PSK plans.  S < 2: no bytes, sync index -1.
+ * Soft values: one int8 per product, the hard bit's sign, the magnitude of
+ * amr_psk_soft_host's BPSK rule, aligned to the bytes as amr_psk_demod_soft_*.
+ * Acquisition, per stream of n samples:
+ *   u[m]  = sum over i < spc of x[m + i] * Wc[(m + i) % L],  m = 0 .. n - spc,
+ *           sequential in i from 0.0, the product rounded first
+ *   M     = (n - L + 1) / L if n >= 2 L - 1, else 0
+ *   y     = sum over j < C of cs[j] * u[d + s L + j spc], sequential in j from 0.0
+ *   g_q[d] = sum over s = 64 q .. min(64 q + 64, M) - 1 of yr*yr + yi*yi, sequential from 0.0
+ *   P[d]  = g_0[d] + g_1[d] + ...          sequential in q from 0.0
+ *   o     = best after: best = 0; for d = 1 .. L - 1: if (P[d] > P[best]) best = d
+ * The acquisition buffers are allocated on the plan's first acquiring call
+ * (then part of amr_dsss_plan_scratch_bytes); amr_dsss_acquire_bytes_estimate is
+ * their size by host arithmetic (< 0: bad shape).  n_samples < 2^31 to acquire. */
+typedef struct amr_dsss_plan amr_dsss_plan;
+#define AMR_TD_DESPREAD 0     /* k_dsss_despread */
+#define AMR_TD_SLICE 1        /* k_dsss_slice */
+#define AMR_TD_SYNC_PACK 2    /* sync search and byte pack; in a soft call k_dsss_soft too (it reads their window) */
+#define AMR_TD_LAUNCH 3       /* the whole launch */
+#define AMR_TD_ACQUIRE 4      /* k_dsss_acquire and k_dsss_acq_max of an acquiring call (inside AMR_TD_LAUNCH) */
+#define AMR_TD_COUNT 5
+int amr_dsss_plan_create(amr_dsss_plan **plan, int device, int64_t n_samples, int64_t spc, int C, int64_t cyc,
+                         const double *Wc, const double *T, const double *cs, int64_t max_streams);
+int amr_dsss_plan_destroy(amr_dsss_plan *plan);
+int amr_dsss_plan_synchronize(amr_dsss_plan *plan);
+int amr_dsss_plan_enable_timing(amr_dsss_plan *plan, int on);
+/* milliseconds of each AMR_TD_* slot in the last call (-1 = not run) */
+int amr_dsss_plan_timings(amr_dsss_plan *plan, float *ms, int count);
+/* bytes an output row needs ((S - 1) / 8 + 1), or -1 */
+int64_t amr_dsss_plan_out_capacity(const amr_dsss_plan *plan);
+/* device bytes the plan holds now, and (host arithmetic) what a plan of this
+ * shape holds once its host entries have staged a full batch; < 0: bad shape */
+int64_t amr_dsss_plan_scratch_bytes(const amr_dsss_plan *plan);
+int64_t amr_dsss_plan_bytes_estimate(int64_t n_samples, int64_t spc, int C, int64_t max_streams);
+int64_t amr_dsss_acquire_bytes_estimate(int64_t n_samples, int64_t spc, int C, int64_t max_streams);
+/* the PSK entries' shapes and argument contract.  soft [n_streams][soft_stride]
+ * (soft_stride >= 8 * out_capacity) and offset [n_streams] may be NULL; acquire
+ * != 0: every stream is read from its acquired offset, else from 0 (offset then
+ * receives zeros).  Acquisition, despreader, slicer, sync / pack and soft values
+ * are queued on the plan's stream with no host round trip in between. */
+int amr_dsss_demod_host(amr_dsss_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                        uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx, int8_t *soft,
+                        int64_t soft_stride, int64_t *offset, int acquire);
+int amr_dsss_demod_device(amr_dsss_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                          uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                          int8_t *d_soft, int64_t soft_stride, int64_t *d_offset, int acquire);
+/* the acquisition stage alone: offset [n_streams] and P [n_streams][L]; P may
+ * be NULL.  _device: device pointers, queued on the plan's stream. */
+int amr_dsss_acquire_host(amr_dsss_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                          int64_t *offset, double *P);
+int amr_dsss_acquire_device(amr_dsss_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                            int64_t *d_offset, double *d_P);
+/* the despreader alone at given offsets: Y [n_streams][S][2] of shift(x[b],
+ * offset[b]); an offset outside [0, L - 1] is AMR_E_INVALID before any device work */
+int amr_dsss_symbols_at_host(amr_dsss_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                             const int64_t *offset, double *Y);
+/* the slicer and soft stages alone on given Y [n_streams][n_sym][2]: words
+ * [n_streams][max(1, ceil((n_sym - 1) / 32))] (MSB first), soft
+ * [n_streams][n_sym - 1] (every bit from 0) */
+int amr_dsss_slice_host(const double *Y, int64_t n_streams, int64_t n_sym, uint32_t *words);
+int amr_dsss_soft_host(const double *Y, int64_t n_streams, int64_t n_sym, int8_t *soft);
+/* spread_modulate: the bits [1,0]*40 + payload (MSB first) as symbols s[0] =
+ * +1.0, s[k+1] = -s[k] if bit k is 1 else s[k]; sample i of symbol k is
+ * float32(s[k] * (sg[i] * Sn[i])): the sine is the caller's table, so the
+ * output is the restatement's bit for bit.  No envelope ramp.  A frame of an
+ * n_bytes payload is (81 + 8 n_bytes) * L samples; out / pcm / n_out as
+ * amr_modulate_host. */
+int amr_dsss_modulate_host(int64_t spc, int C, int64_t cyc, const double *cs, const double *Sn, const uint8_t *data,
                            int64_t data_stride, const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride,
                            int64_t n_out, int16_t *pcm, int64_t pcm_stride);
 
