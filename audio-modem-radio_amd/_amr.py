@@ -192,27 +192,35 @@ def hell_demod(x: np.ndarray, baud, samp_rate, elem=None, energy=False):
     return (outs, en) if energy else outs
 
 
-def modulate(mode: int, datas, baud, f0, f1=0.0, samp_rate=96000, n_out=None, pcm=False):
-    """Batched transmit side on the GPU (amr_modulate_host): the reference
-    modulator's float32 waveform of every payload in `datas` (modem.py:28-65,
-    138-186, 270-295), cut / zero-padded to n_out samples (default: the
-    longest natural length).  pcm=True also returns wav_from_array's int16."""
-    require_gpu()
+def _modulate_call(datas, n_out, pcm, call):
+    """The *_modulate_host entries' common arguments: the payloads packed into [n][stride] uint8 with their
+    lengths, out [n][n_out] float32 and, with pcm, int16.  call(data, data_stride, n_bytes, n, out,
+    out_stride, n_out, pcm, pcm_stride) -> rc; returns (rc, out or (out, pcm))."""
     n = len(datas)
     lens = np.array([len(d) for d in datas], np.int64)
-    if n_out is None:
-        n_out = max((tx_samples(mode, int(x), baud, samp_rate) for x in lens), default=0)
     stride = max(1, int(lens.max()) if n else 1)
     buf = np.zeros((max(n, 1), stride), np.uint8)
     for i, d in enumerate(datas):
         buf[i, :len(d)] = np.frombuffer(bytes(d), np.uint8)
     out = np.zeros((n, n_out), np.float32)
     pc = np.zeros((n, n_out), np.int16) if pcm else None
-    rc = lib().amr_modulate_host(mode, float(baud), float(f0), float(f1), float(samp_rate), ptr(buf), stride,
-                                 ptr(lens), n, ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out)
+    rc = call(ptr(buf), stride, ptr(lens), n, ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out)
+    return rc, ((out, pc) if pcm else out)
+
+
+def modulate(mode: int, datas, baud, f0, f1=0.0, samp_rate=96000, n_out=None, pcm=False):
+    """Batched transmit side on the GPU (amr_modulate_host): the reference
+    modulator's float32 waveform of every payload in `datas` (modem.py:28-65,
+    138-186, 270-295), cut / zero-padded to n_out samples (default: the
+    longest natural length).  pcm=True also returns wav_from_array's int16."""
+    require_gpu()
+    if n_out is None:
+        n_out = max((tx_samples(mode, len(d), baud, samp_rate) for d in datas), default=0)
+    rc, res = _modulate_call(datas, n_out, pcm, lambda *a: lib().amr_modulate_host(
+        mode, float(baud), float(f0), float(f1), float(samp_rate), *a))
     if rc != AMR_OK:
         _raise_tx(rc)
-    return (out, pc) if pcm else out
+    return res
 
 
 def psk_slice(kind: str, sym: np.ndarray) -> np.ndarray:
@@ -1007,29 +1015,32 @@ def _rows(x: np.ndarray):
     return x, (x.strides[0] // x.itemsize if B > 1 else n)
 
 
-class OfdmPlan:
-    """A device plan of the ofdm demodulator: W in HBM + Y and the bit words for max_streams streams."""
+class _SymPlan:
+    """What the symbol modems' plans (OfdmPlan, DsssPlan) share, over the amr_<_abi>_* entries: the handle's
+    lifetime, the batching of a call into max_streams streams at a time, the host demodulation and stage
+    loops, and the plan accessors.  A subclass sets _abi and _slots and calls _create from its __init__."""
+    _abi = ""
+    _slots = ()
 
-    def __init__(self, n: int, baud, carrier, num_subcarriers, samp_rate=96000, max_streams=64, device=None):
-        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
-        self.sps, self.L, self.Ncp, self.Nu, self.bins, W = design_ofdm(baud, carrier, num_subcarriers, samp_rate)
-        self.K = len(self.bins)
-        self.S = self.n // self.L
+    def _fn(self, name):
+        return getattr(lib(), f"amr_{self._abi}_{name}")
+
+    def _create(self, device, max_streams, *design):
+        """amr_<_abi>_plan_create(&handle, device, *design, max_streams)"""
         require_gpu()
         self.device = default_device() if device is None else device
         self.max_streams = int(max_streams)
         h = ctypes.c_void_p()
-        check(lib().amr_ofdm_plan_create(ctypes.byref(h), self.device, self.n, self.sps, self.K, ptr(self.bins),
-                                         ptr(W), self.max_streams))
+        check(self._fn("plan_create")(ctypes.byref(h), self.device, *design, self.max_streams))
         self.handle = h
-        self.out_cap = int(lib().amr_ofdm_plan_out_capacity(h))
+        self.out_cap = int(self._fn("plan_out_capacity")(h))
         self.lock = threading.Lock()
 
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and _lib is not None:
             try:
-                _lib.amr_ofdm_plan_destroy(h)
+                getattr(_lib, f"amr_{self._abi}_plan_destroy")(h)
             except Exception:
                 pass
             self.handle = None
@@ -1039,120 +1050,110 @@ class OfdmPlan:
         for s0 in range(0, x.shape[0], self.max_streams):
             yield s0, x[s0:s0 + self.max_streams], stride
 
+    def _demod(self, x, entry, soft, tail):
+        """A host demodulation entry on x, max_streams streams at a time: (list[bytes], sync, list[int8 array]
+        or None, offsets int64 [B]).  tail(sv, of): the entry's arguments after sync_idx, from sv = (soft
+        or NULL, soft_stride) and the batch's offsets array `of` (left zero where the entry has none)."""
+        outs, softs = [], []
+        syncs, offs = np.empty(x.shape[0], np.int64), np.zeros(x.shape[0], np.int64)
+        cap = max(self.out_cap, 1)
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            out = np.empty((nb, cap), np.uint8)
+            sv = np.empty((nb, 8 * cap), np.int8) if soft else None
+            ln, sy, of = np.empty(nb, np.int64), np.empty(nb, np.int64), offs[s0:s0 + nb]
+            with self.lock:
+                check(self._fn(entry)(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap, ptr(ln),
+                                      ptr(sy), *tail((ptr(sv) if soft else None, 8 * cap), of)))
+            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
+            if soft:
+                softs += [sv[i, :8 * ln[i]].copy() for i in range(nb)]
+            syncs[s0:s0 + nb] = sy
+        return outs, syncs, (softs if soft else None), offs
+
+    def _stage(self, x, entry, outs, offsets=None):
+        """A stage entry on x, max_streams streams at a time: entry(plan, x, dtype, B, x_stride[, offsets],
+        *outs), each of `outs` a C-contiguous [B][...] array the batches fill; returns outs."""
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            ob = None if offsets is None else np.ascontiguousarray(offsets[s0:s0 + nb])
+            with self.lock:
+                check(self._fn(entry)(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride,
+                                      *(() if ob is None else (ptr(ob),)), *(ptr(o[s0:s0 + nb]) for o in outs)))
+        return outs
+
+    def scratch_bytes(self) -> int:
+        """Device bytes this plan holds (tables, Y, words + host-API staging + the acquisition buffers once used)."""
+        return int(self._fn("plan_scratch_bytes")(self.handle)) if self.handle else 0
+
+    def enable_timing(self, on=True):
+        check(self._fn("plan_enable_timing")(self.handle, 1 if on else 0))
+
+    def synchronize(self):
+        check(self._fn("plan_synchronize")(self.handle))
+
+    def timings(self) -> dict:
+        ms = (ctypes.c_float * len(self._slots))()
+        check(self._fn("plan_timings")(self.handle, ms, len(self._slots)))
+        return {k: float(v) for k, v in zip(self._slots, ms) if v >= 0}
+
+
+def _plan_acquires(pl, key, nbytes):
+    """A cached plan about to acquire: the first time, the cache makes room for its acquisition
+    buffers (nbytes(): the modem's amr_*_acquire_bytes_estimate)."""
+    if not getattr(pl, "acquires", False):
+        plan_cache.reserve(key, max(0, int(nbytes())))
+        pl.acquires = True
+
+
+class OfdmPlan(_SymPlan):
+    """A device plan of the ofdm demodulator: W in HBM + Y and the bit words for max_streams streams."""
+    _abi = "ofdm"
+    _slots = TO_SLOTS
+
+    def __init__(self, n: int, baud, carrier, num_subcarriers, samp_rate=96000, max_streams=64, device=None):
+        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
+        self.sps, self.L, self.Ncp, self.Nu, self.bins, W = design_ofdm(baud, carrier, num_subcarriers, samp_rate)
+        self.K = len(self.bins)
+        self.S = self.n // self.L
+        self._create(device, max_streams, self.n, self.sps, self.K, ptr(self.bins), ptr(W))
+
     def demod_host(self, x: np.ndarray, acquire=False):
         """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync);
         acquire=True: each stream from its own acquired offset, (list[bytes], sync, offsets)."""
         if acquire:
             outs, syncs, _, offs = self.demod_acq_host(x)
             return outs, syncs, offs
-        outs, syncs = [], np.empty(x.shape[0], np.int64)
-        cap = max(self.out_cap, 1)
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            out = np.empty((nb, cap), np.uint8)
-            ln = np.empty(nb, np.int64)
-            sy = np.empty(nb, np.int64)
-            with self.lock:
-                check(lib().amr_ofdm_demod_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
-                                                ptr(ln), ptr(sy)))
-            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
-            syncs[s0:s0 + nb] = sy
-        return outs, syncs
+        return self._demod(x, "demod_host", False, lambda sv, of: ())[:2]
 
     def demod_soft_host(self, x: np.ndarray, acquire=False):
         """demod_host with the soft values: (list[bytes], sync, list[int8 array]);
         soft[i][j] belongs to bit j of outs[i].  acquire=True: the offsets as a fourth value."""
         if acquire:
             return self.demod_acq_host(x, soft=True)
-        outs, softs, syncs = [], [], np.empty(x.shape[0], np.int64)
-        cap = max(self.out_cap, 1)
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            out = np.empty((nb, cap), np.uint8)
-            soft = np.empty((nb, 8 * cap), np.int8)
-            ln = np.empty(nb, np.int64)
-            sy = np.empty(nb, np.int64)
-            with self.lock:
-                check(lib().amr_ofdm_demod_soft_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out),
-                                                     cap, ptr(ln), ptr(sy), ptr(soft), 8 * cap))
-            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
-            softs += [soft[i, :8 * ln[i]].copy() for i in range(nb)]
-            syncs[s0:s0 + nb] = sy
-        return outs, syncs, softs
+        return self._demod(x, "demod_soft_host", True, lambda sv, of: sv)[:3]
 
     def symbols(self, x: np.ndarray) -> np.ndarray:
         """The DFT stage alone (amr_ofdm_symbols_host): Y [B][S][K] complex128."""
-        Y = np.zeros((x.shape[0], self.S, self.K, 2))
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            yb = np.zeros((nb, self.S, self.K, 2))
-            with self.lock:
-                check(lib().amr_ofdm_symbols_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(yb)))
-            Y[s0:s0 + nb] = yb
+        Y, = self._stage(x, "symbols_host", [np.zeros((x.shape[0], self.S, self.K, 2))])
         return Y.view(np.complex128)[..., 0]
 
     def demod_acq_host(self, x: np.ndarray, soft=False):
         """Acquisition, then the demodulation of every stream from its offset (amr_ofdm_demod_acq_host):
         (list[bytes], sync, list[int8 array] or None, offsets int64 [B])."""
-        outs, softs = [], []
-        syncs, offs = np.empty(x.shape[0], np.int64), np.empty(x.shape[0], np.int64)
-        cap = max(self.out_cap, 1)
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            out = np.empty((nb, cap), np.uint8)
-            sv = np.empty((nb, 8 * cap), np.int8) if soft else None
-            ln, sy, of = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty(nb, np.int64)
-            with self.lock:
-                check(lib().amr_ofdm_demod_acq_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
-                                                    ptr(ln), ptr(sy), ptr(sv) if soft else None, 8 * cap, ptr(of)))
-            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
-            if soft:
-                softs += [sv[i, :8 * ln[i]].copy() for i in range(nb)]
-            syncs[s0:s0 + nb] = sy
-            offs[s0:s0 + nb] = of
-        return outs, syncs, (softs if soft else None), offs
+        return self._demod(x, "demod_acq_host", soft, lambda sv, of: (*sv, ptr(of)))
 
     def acquire(self, x: np.ndarray):
         """The acquisition stage alone (amr_ofdm_acquire_host): (offset int64 [B], dhat int64 [B], E float64 [B][L])."""
         B = x.shape[0]
-        off, dh, E = np.empty(B, np.int64), np.empty(B, np.int64), np.empty((B, self.L))
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            of, d, e = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty((nb, self.L))
-            with self.lock:
-                check(lib().amr_ofdm_acquire_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(of), ptr(d),
-                                                  ptr(e)))
-            off[s0:s0 + nb], dh[s0:s0 + nb], E[s0:s0 + nb] = of, d, e
-        return off, dh, E
+        return tuple(self._stage(x, "acquire_host", [np.empty(B, np.int64), np.empty(B, np.int64),
+                                                     np.empty((B, self.L))]))
 
     def symbols_at(self, x: np.ndarray, offsets) -> np.ndarray:
         """The DFT stage at given per-stream offsets (amr_ofdm_symbols_at_host): Y [B][S][K] complex128."""
-        offsets = np.ascontiguousarray(offsets, np.int64)
-        Y = np.zeros((x.shape[0], self.S, self.K, 2))
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            yb = np.zeros((nb, self.S, self.K, 2))
-            ob = np.ascontiguousarray(offsets[s0:s0 + nb])
-            with self.lock:
-                check(lib().amr_ofdm_symbols_at_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(ob),
-                                                     ptr(yb)))
-            Y[s0:s0 + nb] = yb
+        Y, = self._stage(x, "symbols_at_host", [np.zeros((x.shape[0], self.S, self.K, 2))],
+                         np.ascontiguousarray(offsets, np.int64))
         return Y.view(np.complex128)[..., 0]
-
-    def scratch_bytes(self) -> int:
-        """Device bytes this plan holds (W, Y, words + host-API staging + the acquisition buffers once used)."""
-        return int(lib().amr_ofdm_plan_scratch_bytes(self.handle)) if self.handle else 0
-
-    def enable_timing(self, on=True):
-        check(lib().amr_ofdm_plan_enable_timing(self.handle, 1 if on else 0))
-
-    def synchronize(self):
-        check(lib().amr_ofdm_plan_synchronize(self.handle))
-
-    def timings(self) -> dict:
-        ms = (ctypes.c_float * len(TO_SLOTS))()
-        check(lib().amr_ofdm_plan_timings(self.handle, ms, len(TO_SLOTS)))
-        return {k: float(v) for k, v in zip(TO_SLOTS, ms) if v >= 0}
 
 
 def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int, acquire=False) -> OfdmPlan:
@@ -1168,9 +1169,8 @@ def get_ofdm_plan(n: int, baud, carrier, num_subcarriers, samp_rate, batch: int,
         return max(0, int(lib().amr_ofdm_plan_bytes_estimate(int(n), sps, K, m)))
     pl = plan_cache.get(key, need, lambda m: OfdmPlan(n, baud, carrier, K, samp_rate, max_streams=m, device=dev),
                         estimate)
-    if acquire and not getattr(pl, "acquires", False):
-        plan_cache.reserve(key, max(0, int(lib().amr_ofdm_acquire_bytes_estimate(int(n), sps, K, pl.max_streams))))
-        pl.acquires = True
+    if acquire:
+        _plan_acquires(pl, key, lambda: lib().amr_ofdm_acquire_bytes_estimate(int(n), sps, K, pl.max_streams))
     return pl
 
 
@@ -1186,23 +1186,24 @@ def ofdm_modulate(datas, baud, carrier, num_subcarriers, samp_rate=96000, n_out=
     float32, cut / zero-padded to n_out (default: the longest natural length);
     pcm=True also returns wav_from_array's int16."""
     K = int(num_subcarriers)
-    n = len(datas)
-    lens = np.array([len(d) for d in datas], np.int64)
-    natural = [ofdm_tx_samples(int(v), baud, carrier, K, samp_rate) for v in lens]     # the geometry's ValueError
+    natural = [ofdm_tx_samples(len(d), baud, carrier, K, samp_rate) for d in datas]    # the geometry's ValueError
     ofdm_geometry(baud, carrier, K, samp_rate)
     require_gpu()
     if n_out is None:
         n_out = max(natural, default=0)
-    stride = max(1, int(lens.max()) if n else 1)
-    buf = np.zeros((max(n, 1), stride), np.uint8)
-    for i, d in enumerate(datas):
-        buf[i, :len(d)] = np.frombuffer(bytes(d), np.uint8)
-    out = np.zeros((n, n_out), np.float32)
-    pc = np.zeros((n, n_out), np.int16) if pcm else None
     check(lib().amr_set_device(default_device()))
-    check(lib().amr_ofdm_modulate_host(float(baud), float(carrier), float(samp_rate), K, ptr(buf), stride, ptr(lens),
-                                       n, ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out))
-    return (out, pc) if pcm else out
+    rc, res = _modulate_call(datas, n_out, pcm, lambda *a: lib().amr_ofdm_modulate_host(
+        float(baud), float(carrier), float(samp_rate), K, *a))
+    check(rc)
+    return res
+
+
+def _slice_bits(B: int, nbits: int, call) -> np.ndarray:
+    """A *_slice_host entry's words as bits: call(words) fills uint32 [B][max(1, ceil(nbits / 32))], MSB
+    first; the first nbits of every row come back as uint8."""
+    words = np.zeros((B, max(1, (nbits + 31) // 32)), np.uint32)
+    check(call(ptr(words)))
+    return np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)[:, :nbits]
 
 
 def ofdm_slice(Y: np.ndarray) -> np.ndarray:
@@ -1211,12 +1212,7 @@ def ofdm_slice(Y: np.ndarray) -> np.ndarray:
     require_gpu()
     Y = np.ascontiguousarray(Y, np.complex128)
     B, S, K = Y.shape
-    nbits = max(0, 2 * K * (S - 1))
-    nw = max(1, (nbits + 31) // 32)
-    words = np.zeros((B, nw), np.uint32)
-    check(lib().amr_ofdm_slice_host(ptr(Y), B, S, K, ptr(words)))
-    bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
-    return bits[:, :nbits]
+    return _slice_bits(B, max(0, 2 * K * (S - 1)), lambda w: lib().amr_ofdm_slice_host(ptr(Y), B, S, K, w))
 
 
 def ofdm_soft(Y: np.ndarray) -> np.ndarray:
@@ -1274,102 +1270,34 @@ def design_dsss(baud, carrier, code=None, samp_rate=96000):
     return spc, L, cyc, c, Wc, T, Sn, cs
 
 
-class DsssPlan:
+class DsssPlan(_SymPlan):
     """A device plan of the spread demodulator: the tables in HBM + Y and the bit words for max_streams streams."""
+    _abi = "dsss"
+    _slots = TD_SLOTS
 
     def __init__(self, n: int, baud, carrier, code=None, samp_rate=96000, max_streams=64, device=None):
         self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
         self.spc, self.L, self.cyc, self.code, Wc, T, _, cs = design_dsss(baud, carrier, code, samp_rate)
         self.C = int(self.code.size)
         self.S = self.n // self.L
-        require_gpu()
-        self.device = default_device() if device is None else device
-        self.max_streams = int(max_streams)
-        h = ctypes.c_void_p()
-        check(lib().amr_dsss_plan_create(ctypes.byref(h), self.device, self.n, self.spc, self.C, self.cyc, ptr(Wc),
-                                         ptr(T), ptr(cs), self.max_streams))
-        self.handle = h
-        self.out_cap = int(lib().amr_dsss_plan_out_capacity(h))
-        self.lock = threading.Lock()
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _lib is not None:
-            try:
-                _lib.amr_dsss_plan_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
-
-    def _batches(self, x):
-        x, stride = _rows(x)
-        for s0 in range(0, x.shape[0], self.max_streams):
-            yield s0, x[s0:s0 + self.max_streams], stride
+        self._create(device, max_streams, self.n, self.spc, self.C, self.cyc, ptr(Wc), ptr(T), ptr(cs))
 
     def demod_host(self, x: np.ndarray, soft=False, acquire=True):
         """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync,
         list[int8 array] or None, offsets int64 [B]); acquire: each stream from its own acquired offset."""
-        outs, softs = [], []
-        syncs, offs = np.empty(x.shape[0], np.int64), np.empty(x.shape[0], np.int64)
-        cap = max(self.out_cap, 1)
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            out = np.empty((nb, cap), np.uint8)
-            sv = np.empty((nb, 8 * cap), np.int8) if soft else None
-            ln, sy, of = np.empty(nb, np.int64), np.empty(nb, np.int64), np.empty(nb, np.int64)
-            with self.lock:
-                check(lib().amr_dsss_demod_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(out), cap,
-                                                ptr(ln), ptr(sy), ptr(sv) if soft else None, 8 * cap, ptr(of),
-                                                1 if acquire else 0))
-            outs += [out[i, :ln[i]].tobytes() for i in range(nb)]
-            if soft:
-                softs += [sv[i, :8 * ln[i]].copy() for i in range(nb)]
-            syncs[s0:s0 + nb] = sy
-            offs[s0:s0 + nb] = of
-        return outs, syncs, (softs if soft else None), offs
+        return self._demod(x, "demod_host", soft, lambda sv, of: (*sv, ptr(of), 1 if acquire else 0))
 
     def acquire(self, x: np.ndarray):
         """The acquisition stage alone (amr_dsss_acquire_host): (offset int64 [B], P float64 [B][L])."""
         B = x.shape[0]
-        off, P = np.empty(B, np.int64), np.empty((B, self.L))
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            of, pb = np.empty(nb, np.int64), np.empty((nb, self.L))
-            with self.lock:
-                check(lib().amr_dsss_acquire_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(of),
-                                                  ptr(pb)))
-            off[s0:s0 + nb], P[s0:s0 + nb] = of, pb
-        return off, P
+        return tuple(self._stage(x, "acquire_host", [np.empty(B, np.int64), np.empty((B, self.L))]))
 
     def symbols_at(self, x: np.ndarray, offsets=None) -> np.ndarray:
         """The despreader alone at given per-stream offsets, default zeros (amr_dsss_symbols_at_host):
         Y [B][S] complex128."""
         offsets = np.zeros(x.shape[0], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64)
-        Y = np.zeros((x.shape[0], self.S, 2))
-        for s0, xb, stride in self._batches(x):
-            nb = xb.shape[0]
-            yb = np.zeros((nb, self.S, 2))
-            ob = np.ascontiguousarray(offsets[s0:s0 + nb])
-            with self.lock:
-                check(lib().amr_dsss_symbols_at_host(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(ob),
-                                                     ptr(yb)))
-            Y[s0:s0 + nb] = yb
+        Y, = self._stage(x, "symbols_at_host", [np.zeros((x.shape[0], self.S, 2))], offsets)
         return Y.view(np.complex128)[..., 0]
-
-    def scratch_bytes(self) -> int:
-        """Device bytes this plan holds (tables, Y, words + host-API staging + the acquisition buffers once used)."""
-        return int(lib().amr_dsss_plan_scratch_bytes(self.handle)) if self.handle else 0
-
-    def enable_timing(self, on=True):
-        check(lib().amr_dsss_plan_enable_timing(self.handle, 1 if on else 0))
-
-    def synchronize(self):
-        check(lib().amr_dsss_plan_synchronize(self.handle))
-
-    def timings(self) -> dict:
-        ms = (ctypes.c_float * len(TD_SLOTS))()
-        check(lib().amr_dsss_plan_timings(self.handle, ms, len(TD_SLOTS)))
-        return {k: float(v) for k, v in zip(TD_SLOTS, ms) if v >= 0}
 
 
 def get_dsss_plan(n: int, baud, carrier, code, samp_rate, batch: int, acquire=False) -> DsssPlan:
@@ -1385,9 +1313,8 @@ def get_dsss_plan(n: int, baud, carrier, code, samp_rate, batch: int, acquire=Fa
         return max(0, int(lib().amr_dsss_plan_bytes_estimate(int(n), spc, C, m)))
     pl = plan_cache.get(key, need, lambda m: DsssPlan(n, baud, carrier, c, samp_rate, max_streams=m, device=dev),
                         estimate)
-    if acquire and not getattr(pl, "acquires", False):
-        plan_cache.reserve(key, max(0, int(lib().amr_dsss_acquire_bytes_estimate(int(n), spc, C, pl.max_streams))))
-        pl.acquires = True
+    if acquire:
+        _plan_acquires(pl, key, lambda: lib().amr_dsss_acquire_bytes_estimate(int(n), spc, C, pl.max_streams))
     return pl
 
 
@@ -1401,21 +1328,14 @@ def dsss_modulate(datas, baud, carrier, code=None, samp_rate=96000, n_out=None, 
     float32, cut / zero-padded to n_out (default: the longest natural length);
     pcm=True also returns wav_from_array's int16."""
     spc, L, cyc, c, _, _, Sn, cs = design_dsss(baud, carrier, code, samp_rate)   # the geometry's ValueError
-    n = len(datas)
-    lens = np.array([len(d) for d in datas], np.int64)
     require_gpu()
     if n_out is None:
-        n_out = max(((81 + 8 * int(v)) * L for v in lens), default=0)
-    stride = max(1, int(lens.max()) if n else 1)
-    buf = np.zeros((max(n, 1), stride), np.uint8)
-    for i, d in enumerate(datas):
-        buf[i, :len(d)] = np.frombuffer(bytes(d), np.uint8)
-    out = np.zeros((n, n_out), np.float32)
-    pc = np.zeros((n, n_out), np.int16) if pcm else None
+        n_out = max(((81 + 8 * len(d)) * L for d in datas), default=0)
     check(lib().amr_set_device(default_device()))
-    check(lib().amr_dsss_modulate_host(spc, int(c.size), cyc, ptr(cs), ptr(Sn), ptr(buf), stride, ptr(lens), n,
-                                       ptr(out), n_out, n_out, ptr(pc) if pcm else None, n_out))
-    return (out, pc) if pcm else out
+    rc, res = _modulate_call(datas, n_out, pcm, lambda *a: lib().amr_dsss_modulate_host(
+        spc, int(c.size), cyc, ptr(cs), ptr(Sn), *a))
+    check(rc)
+    return res
 
 
 def dsss_slice(Y: np.ndarray) -> np.ndarray:
@@ -1423,11 +1343,7 @@ def dsss_slice(Y: np.ndarray) -> np.ndarray:
     require_gpu()
     Y = np.ascontiguousarray(Y, np.complex128)
     B, S = Y.shape
-    nbits = max(0, S - 1)
-    words = np.zeros((B, max(1, (nbits + 31) // 32)), np.uint32)
-    check(lib().amr_dsss_slice_host(ptr(Y), B, S, ptr(words)))
-    bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
-    return bits[:, :nbits]
+    return _slice_bits(B, max(0, S - 1), lambda w: lib().amr_dsss_slice_host(ptr(Y), B, S, w))
 
 
 def dsss_soft(Y: np.ndarray) -> np.ndarray:

@@ -309,4 +309,9 @@ struct TxParams {
   double inc0, inc1;     // CPFSK phase increments (bit 1 = f0 = mark, bit 0 = f1 = space)
 };
 
+// The sync search and byte packing every modem ends with (util_kernels.hip):
+// words [n_streams][n_words] bits MSB first -> out [n_streams][out_stride], out_len, sync_idx
+hipError_t launch_sync_pack(const uint32_t* words, int64_t n_words, int64_t n_bits, int64_t n_streams, uint8_t* out,
+                            int64_t out_stride, int64_t* out_len, int64_t* sync_idx, hipStream_t st);
+
 }  // namespace amr

@@ -39,8 +39,6 @@ int64_t psk_lane_lp_scratch_doubles(int64_t n_streams, int64_t n, int pad);
 int64_t psk_exact_scratch_bytes(int64_t n_streams, int64_t m2);
 hipError_t launch_synth_tile_noise(const float*, int64_t, int64_t, float*, int64_t, int64_t, float, uint64_t,
                                    hipStream_t);
-hipError_t launch_sync_pack(const uint32_t*, int64_t, int64_t, int64_t, uint8_t*, int64_t, int64_t*, int64_t*,
-                            hipStream_t);
 hipError_t launch_sync_pack_gated(const uint32_t*, int64_t, int64_t, int64_t, uint8_t*, int64_t, int64_t*, int64_t*,
                                   const int32_t*, hipStream_t);
 hipError_t launch_psk_split_bp(const PskBuffers&, const PskParams&, const Iir&, const PskSplit&, hipStream_t);

@@ -36,8 +36,6 @@ hipError_t launch_fsk_decide(const uint8_t*, uint32_t*, int64_t, const FskParams
 hipError_t launch_fsk_split(int, const void*, int64_t, int64_t, double2*, const FskParams&, const FskIir&,
                             const FskSplit&, hipStream_t);
 int64_t fsk_bandpass_scratch_bytes(int64_t n_streams, int64_t n, int pad);
-hipError_t launch_sync_pack(const uint32_t*, int64_t, int64_t, int64_t, uint8_t*, int64_t, int64_t*, int64_t*,
-                            hipStream_t);
 }  // namespace amr
 
 using namespace amr;

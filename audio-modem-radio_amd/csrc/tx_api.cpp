@@ -19,6 +19,7 @@
 #include "amr_internal.h"
 #include "api_common.h"
 #include "dev_mem.h"
+#include "tx_host.h"
 
 namespace amr {
 hipError_t launch_tx(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
@@ -145,36 +146,14 @@ int amr_modulate_host(int mode, double baud, double f0, double f1, double sample
   TxParams p;
   int rc = tx_setup(mode, baud, f0, f1, sample_rate, n_out, &p);
   if (rc) return rc;
-  int64_t maxlen = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    if (n_bytes[i] < 0 || n_bytes[i] > data_stride) return fail(AMR_E_INVALID, "n_bytes out of range");
-    maxlen = n_bytes[i] > maxlen ? n_bytes[i] : maxlen;
-  }
-  if (maxlen > 0 && !data) return fail(AMR_E_INVALID, "amr_modulate_host: NULL data");
-  if (n == 0 || n_out == 0) return AMR_OK;
-  const int64_t stride = maxlen > 0 ? maxlen : 1;
-  const int64_t wb = work_bytes(p, n);
-  const auto bad = [](hipError_t e) {
-    return fail(AMR_E_HIP, std::string("amr_modulate_host: ") + hipGetErrorString(e));
-  };
-  DevBuf d_data, d_nb, d_out, d_pcm, d_work;
-  HIP_TRY_ELSE(d_data.reserve(n * stride, nullptr), bad);
-  HIP_TRY_ELSE(d_nb.reserve(n * 8, nullptr), bad);
-  HIP_TRY_ELSE(d_out.reserve(n * n_out * 4, nullptr), bad);
-  if (pcm) HIP_TRY_ELSE(d_pcm.reserve(n * n_out * 2, nullptr), bad);
-  HIP_TRY_ELSE(d_work.reserve(wb, nullptr), bad);
-  if (maxlen > 0)
-    HIP_TRY_ELSE(memcpy_rows(d_data.get(), stride, data, data_stride, maxlen, n, hipMemcpyHostToDevice), bad);
-  HIP_TRY_ELSE(hipMemcpy(d_nb.get(), n_bytes, (size_t)n * 8, hipMemcpyHostToDevice), bad);
-  rc = amr_modulate_device(nullptr, mode, baud, f0, f1, sample_rate, d_data.as<uint8_t>(), stride,
-                           d_nb.as<int64_t>(), n, d_out.as<float>(), n_out, n_out, d_pcm.as<int16_t>(), n_out,
-                           d_work.get(), wb);
-  if (rc) return rc;
-  HIP_TRY_ELSE(hipDeviceSynchronize(), bad);
-  HIP_TRY_ELSE(memcpy_rows(out, out_stride * 4, d_out.get(), n_out * 4, n_out * 4, n, hipMemcpyDeviceToHost), bad);
-  if (pcm)
-    HIP_TRY_ELSE(memcpy_rows(pcm, pcm_stride * 2, d_pcm.get(), n_out * 2, n_out * 2, n, hipMemcpyDeviceToHost), bad);
-  return AMR_OK;
+  DevBuf d_work;                                     // freed after the round trip has drained the device
+  return modulate_round_trip("amr_modulate_host", data, data_stride, n_bytes, n, out, out_stride, n_out, pcm,
+                             pcm_stride, [&](const TxDev& d) -> int {
+    const int64_t wb = work_bytes(p, n);
+    HIP_TRY_ELSE(d_work.reserve(wb, nullptr), hip_fail_as("amr_modulate_host"));
+    return amr_modulate_device(nullptr, mode, baud, f0, f1, sample_rate, d.data, d.stride, d.n_bytes, n, d.out,
+                               n_out, n_out, d.pcm, n_out, d_work.get(), wb);
+  });
 }
 
 }  // extern "C"

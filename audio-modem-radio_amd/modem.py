@@ -227,47 +227,78 @@ def _ofdm_input(samples) -> np.ndarray:
     return x if x.dtype in _amr.DTYPES else x.astype(np.float64)
 
 
-def _ofdm_batch(x2d, baud, carrier, num_subcarriers, samp_rate, soft=False, acquire=False):
+def _ofdm_demod(plan, x2d, soft, acquire):
+    if soft:
+        outs, _, softs = plan.demod_soft_host(x2d, acquire=acquire)[:3]
+        return outs, softs
+    return plan.demod_host(x2d, acquire=acquire)[0], None
+
+
+def _spread_demod(plan, x2d, soft, acquire):
+    outs, _, softs, _ = plan.demod_host(x2d, soft=soft, acquire=acquire)
+    return outs, softs
+
+
+# what differs between the two symbol modems (ofdm here, spread below) on the way to a plan's host
+# entries: the geometry check, the plan cache's getter and the plan's demodulation as (outs, softs).
+# `shape` in the functions below is ofdm's num_subcarriers / spread's code.
+_SYM = {"ofdm": (_amr.ofdm_geometry, _amr.get_ofdm_plan, _ofdm_demod),
+        "spread": (_amr.dsss_geometry, _amr.get_dsss_plan, _spread_demod)}
+
+
+def _sym_row(name: str, samples) -> np.ndarray:
+    """The one stream of the 1-D entry `name` as a batch of one."""
+    x = _ofdm_input(samples)
+    if x.ndim != 1:
+        raise ValueError(f"{name} expects a 1-D sample array (use {name}_batch)")
+    return x[None, :]
+
+
+def _sym_plan(modem, x2d, baud, carrier, shape, samp_rate, acquire):
+    """(the batch as the kernels read it, its cached plan or None for an empty batch)"""
     x2d = _ofdm_input(x2d)
     if x2d.ndim != 2:
         raise ValueError("batch input must be a 2-D [streams, samples] array")
     B, n = x2d.shape
-    _amr.ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)      # ValueError, also for an empty batch
-    if B == 0:
+    _SYM[modem][0](baud, carrier, shape, samp_rate)                    # ValueError, also for an empty batch
+    return x2d, (_SYM[modem][1](n, baud, carrier, shape, samp_rate, B, acquire=acquire) if B else None)
+
+
+def _sym_batch(modem, x2d, baud, carrier, shape, samp_rate, soft=False, acquire=False):
+    x2d, plan = _sym_plan(modem, x2d, baud, carrier, shape, samp_rate, acquire)
+    if plan is None:
         return ([], []) if soft else []
-    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B, acquire=acquire)
-    if soft:
-        outs, _, softs = plan.demod_soft_host(x2d, acquire=acquire)[:3]
-        return outs, softs
-    return plan.demod_host(x2d, acquire=acquire)[0]
+    outs, softs = _SYM[modem][2](plan, x2d, soft, acquire)
+    return (outs, softs) if soft else outs
+
+
+def _sym_acquire(modem, x2d, baud, carrier, shape, samp_rate) -> np.ndarray:
+    x2d, plan = _sym_plan(modem, x2d, baud, carrier, shape, samp_rate, True)
+    return np.zeros(0, np.int64) if plan is None else plan.acquire(x2d)[0]
 
 
 def ofdm_demodulate(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False) -> bytes:
     """Multi-carrier DQPSK demodulation of one stream, on the GPU.  acquire=True: the
     capture need not start on a symbol boundary (ofdm_acquire's offset is applied)."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("ofdm_demodulate expects a 1-D sample array (use ofdm_demodulate_batch)")
-    return _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, acquire=acquire)[0]
+    x = _sym_row("ofdm_demodulate", samples)
+    return _sym_batch("ofdm", x, baud, carrier, num_subcarriers, samp_rate, acquire=acquire)[0]
 
 
 def ofdm_demodulate_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False) -> list:
     """[B, N] equal-length streams -> B bytes objects (each == ofdm_demodulate(row))."""
-    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, acquire=acquire)
+    return _sym_batch("ofdm", samples, baud, carrier, num_subcarriers, samp_rate, acquire=acquire)
 
 
 def ofdm_demodulate_soft(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False):
     """ofdm_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("ofdm_demodulate_soft expects a 1-D sample array (use ofdm_demodulate_soft_batch)")
-    outs, softs = _ofdm_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
+    x = _sym_row("ofdm_demodulate_soft", samples)
+    outs, softs = _sym_batch("ofdm", x, baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
     return outs[0], softs[0]
 
 
 def ofdm_demodulate_soft_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000, acquire=False):
     """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
-    return _ofdm_batch(samples, baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
+    return _sym_batch("ofdm", samples, baud, carrier, num_subcarriers, samp_rate, soft=True, acquire=acquire)
 
 
 def ofdm_acquire_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> np.ndarray:
@@ -276,23 +307,12 @@ def ofdm_acquire_batch(samples, baud, carrier, num_subcarriers, samp_rate=96000)
     estimated start less half a prefix.  An aligned capture gives -(Ncp // 2).
     A symbol of fewer than 8 samples has no prefix (Ncp = L // 8 = 0): the offset is
     then 0 whatever the capture, and acquire=True decodes as acquire=False does."""
-    x2d = _ofdm_input(samples)
-    if x2d.ndim != 2:
-        raise ValueError("batch input must be a 2-D [streams, samples] array")
-    B, n = x2d.shape
-    _amr.ofdm_geometry(baud, carrier, num_subcarriers, samp_rate)
-    if B == 0:
-        return np.zeros(0, np.int64)
-    plan = _amr.get_ofdm_plan(n, baud, carrier, num_subcarriers, samp_rate, B, acquire=True)
-    return plan.acquire(x2d)[0]
+    return _sym_acquire("ofdm", samples, baud, carrier, num_subcarriers, samp_rate)
 
 
 def ofdm_acquire(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> int:
     """ofdm_acquire_batch of one stream."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("ofdm_acquire expects a 1-D sample array (use ofdm_acquire_batch)")
-    return int(ofdm_acquire_batch(x[None, :], baud, carrier, num_subcarriers, samp_rate)[0])
+    return int(ofdm_acquire_batch(_sym_row("ofdm_acquire", samples), baud, carrier, num_subcarriers, samp_rate)[0])
 
 
 # ---------------------------------------------------------------------------
@@ -301,45 +321,28 @@ def ofdm_acquire(samples, baud, carrier, num_subcarriers, samp_rate=96000) -> in
 # differentially.  A capture may start anywhere: acquisition (the default)
 # finds the code phase by a sliding code correlation over every sample offset
 # of a bit.  Samples as ofdm reads them.
-def _spread_batch(x2d, baud, carrier, code, samp_rate, soft=False, acquire=True):
-    x2d = _ofdm_input(x2d)
-    if x2d.ndim != 2:
-        raise ValueError("batch input must be a 2-D [streams, samples] array")
-    B, n = x2d.shape
-    _amr.dsss_geometry(baud, carrier, code, samp_rate)                 # ValueError, also for an empty batch
-    if B == 0:
-        return ([], []) if soft else []
-    plan = _amr.get_dsss_plan(n, baud, carrier, code, samp_rate, B, acquire=acquire)
-    outs, _, softs, _ = plan.demod_host(x2d, soft=soft, acquire=acquire)
-    return (outs, softs) if soft else outs
-
-
 def spread_demodulate(samples, baud, carrier, code=None, samp_rate=96000, acquire=True) -> bytes:
     """Direct-sequence DBPSK demodulation of one stream, on the GPU.  acquire=False: the capture
     starts on a bit boundary (offset 0); the default finds the boundary first (spread_acquire)."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("spread_demodulate expects a 1-D sample array (use spread_demodulate_batch)")
-    return _spread_batch(x[None, :], baud, carrier, code, samp_rate, acquire=acquire)[0]
+    x = _sym_row("spread_demodulate", samples)
+    return _sym_batch("spread", x, baud, carrier, code, samp_rate, acquire=acquire)[0]
 
 
 def spread_demodulate_batch(samples, baud, carrier, code=None, samp_rate=96000, acquire=True) -> list:
     """[B, N] equal-length streams -> B bytes objects (each == spread_demodulate(row))."""
-    return _spread_batch(samples, baud, carrier, code, samp_rate, acquire=acquire)
+    return _sym_batch("spread", samples, baud, carrier, code, samp_rate, acquire=acquire)
 
 
 def spread_demodulate_soft(samples, baud, carrier, code=None, samp_rate=96000, acquire=True):
     """spread_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("spread_demodulate_soft expects a 1-D sample array (use spread_demodulate_soft_batch)")
-    outs, softs = _spread_batch(x[None, :], baud, carrier, code, samp_rate, soft=True, acquire=acquire)
+    x = _sym_row("spread_demodulate_soft", samples)
+    outs, softs = _sym_batch("spread", x, baud, carrier, code, samp_rate, soft=True, acquire=acquire)
     return outs[0], softs[0]
 
 
 def spread_demodulate_soft_batch(samples, baud, carrier, code=None, samp_rate=96000, acquire=True):
     """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
-    return _spread_batch(samples, baud, carrier, code, samp_rate, soft=True, acquire=acquire)
+    return _sym_batch("spread", samples, baud, carrier, code, samp_rate, soft=True, acquire=acquire)
 
 
 def spread_acquire_batch(samples, baud, carrier, code=None, samp_rate=96000) -> np.ndarray:
@@ -347,23 +350,12 @@ def spread_acquire_batch(samples, baud, carrier, code=None, samp_rate=96000) -> 
     stream's bits begin: the first maximum over the offsets of a bit of the
     despread energy summed over the capture.  A bit boundary only: which bit is which is the
     sync word's business."""
-    x2d = _ofdm_input(samples)
-    if x2d.ndim != 2:
-        raise ValueError("batch input must be a 2-D [streams, samples] array")
-    B, n = x2d.shape
-    _amr.dsss_geometry(baud, carrier, code, samp_rate)
-    if B == 0:
-        return np.zeros(0, np.int64)
-    plan = _amr.get_dsss_plan(n, baud, carrier, code, samp_rate, B, acquire=True)
-    return plan.acquire(x2d)[0]
+    return _sym_acquire("spread", samples, baud, carrier, code, samp_rate)
 
 
 def spread_acquire(samples, baud, carrier, code=None, samp_rate=96000) -> int:
     """spread_acquire_batch of one stream."""
-    x = _ofdm_input(samples)
-    if x.ndim != 1:
-        raise ValueError("spread_acquire expects a 1-D sample array (use spread_acquire_batch)")
-    return int(spread_acquire_batch(x[None, :], baud, carrier, code, samp_rate)[0])
+    return int(spread_acquire_batch(_sym_row("spread_acquire", samples), baud, carrier, code, samp_rate)[0])
 
 
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:

@@ -438,3 +438,122 @@ def test_end_to_end_coded_chain_at_random_delays():
     rows = [s[16:16 + 8 * Lc] for s in softs]
     assert [m for m, _ in sc.soft_decode_batch(rows)] == msgs
     assert fec.ViterbiDecoder().decode_soft_batch(rows) == msgs
+
+
+# ---- 4. the host layer ofdm shares with spread (sym_plan.h), at a small shape ----------------
+# K = 3, sps = 4: L = 12, Ncp = 1; five symbols and a tail of 3: 24 bits, out_cap 4.  The same cases as
+# test_gpu_spread.py's section 7.
+SMALL = cfg(3, 4)
+SMALL_N = 5 * 12 + 3
+_small = {}
+
+
+def small(dt):
+    """(five rows of a wider array, poisoned behind n; the restatement's acquired (bytes, soft, sync, o) and
+    unacquired (bytes, soft, sync) of every row), computed once per module."""
+    if dt not in _small:
+        wide = np.random.default_rng(12).normal(0, 0.3, (5, SMALL_N + 4))
+        wide = np.round(wide * 8000).astype(np.int16) if dt == "i16" else wide.astype(np.float32)
+        wide[:, SMALL_N:] = 32767 if dt == "i16" else np.nan
+        x = wide[:, :SMALL_N]
+        _small[dt] = (x, [ac.demod_soft(r, *SMALL) for r in x], [oc.demod_soft(r, *SMALL) for r in x])
+    return _small[dt]
+
+
+@pytest.mark.parametrize("dt", ["f32", "i16"])
+def test_small_two_batches_of_wider_rows(dt):
+    """Five streams through a plan of three (a full batch and a short one), x_stride > n: every host entry."""
+    from test_gpu_ofdm import want_Y
+    x, acq, plain = small(dt)
+    assert oc.geometry(*SMALL)[1:3] == (12, 1) and x.strides[0] == (SMALL_N + 4) * x.itemsize
+    assert all(len(w[0]) == 3 for w in plain)
+    pl = plan_for(SMALL_N, SMALL, 3)
+    assert pl.out_cap == 4
+    outs, syncs = pl.demod_host(x)
+    assert outs == [w[0] for w in plain] and list(syncs) == [w[2] for w in plain]
+    outs, syncs, softs = pl.demod_soft_host(x)
+    assert outs == [w[0] for w in plain] and list(syncs) == [w[2] for w in plain]
+    assert all(s.dtype == np.int8 and np.array_equal(s, w[1]) for s, w in zip(softs, plain))
+    outs, syncs, softs, offs = pl.demod_acq_host(x, soft=True)
+    assert outs == [w[0] for w in acq] and list(syncs) == [w[2] for w in acq] and list(offs) == [w[3] for w in acq]
+    assert all(np.array_equal(s, w[1]) for s, w in zip(softs, acq))
+    outs, syncs, offs = pl.demod_host(x, acquire=True)
+    assert outs == [w[0] for w in acq] and list(syncs) == [w[2] for w in acq] and list(offs) == [w[3] for w in acq]
+    off, dh, E = check_acquire(pl, x, SMALL, dt)
+    assert list(off) == [w[3] for w in acq]
+    assert same_bits(pl.symbols(x), want_Y(x, SMALL))
+    assert same_bits(pl.symbols_at(x, off), want_Y_at(x, off, SMALL))
+
+
+@pytest.mark.parametrize("dt", ["f32", "i16"])
+def test_small_host_soft_rows_are_cut(dt):
+    """soft_stride above 8 * out_cap with a sentinel in the slack, out_stride at its minimum: the row is cut at
+    8 * out_len[i] and nothing behind it is written."""
+    import _amr
+    x, acq, plain = small(dt)
+    x = np.ascontiguousarray(x[:3])
+    pl = plan_for(SMALL_N, SMALL, 3)
+    lib, cap = _amr.lib(), pl.out_cap
+    for acquire, want in ((False, plain), (True, acq)):
+        out, ln, sy = np.zeros((3, cap - 1), np.uint8), np.zeros(3, np.int64), np.zeros(3, np.int64)
+        soft, off = np.full((3, 8 * cap + 5), 77, np.int8), np.full(3, -99, np.int64)
+        args = (pl.handle, _amr.ptr(x), _amr.DTYPES[x.dtype], 3, SMALL_N, _amr.ptr(out), cap - 1, _amr.ptr(ln),
+                _amr.ptr(sy), _amr.ptr(soft), 8 * cap + 5)
+        _amr.check(lib.amr_ofdm_demod_acq_host(*args, _amr.ptr(off)) if acquire else lib.amr_ofdm_demod_soft_host(*args))
+        assert [out[i, :ln[i]].tobytes() for i in range(3)] == [w[0] for w in want[:3]]
+        assert list(sy) == [w[2] for w in want[:3]] and list(ln) == [len(w[0]) for w in want[:3]] and min(ln) > 0
+        if acquire:
+            assert list(off) == [w[3] for w in want[:3]]
+        for i in range(3):
+            assert np.array_equal(soft[i, :8 * ln[i]], want[i][1]) and np.all(soft[i, 8 * ln[i]:] == 77), (acquire, i)
+
+
+def test_small_empty_batch_and_fewer_than_two_symbols():
+    import _amr
+    lib = _amr.lib()
+    pl = plan_for(SMALL_N, SMALL, 3)
+    h, F32 = pl.handle, _amr.DTYPE_F32
+    assert lib.amr_ofdm_demod_host(h, None, F32, 0, SMALL_N, None, 4, None, None) == _amr.AMR_OK
+    assert lib.amr_ofdm_demod_soft_host(h, None, F32, 0, SMALL_N, None, 4, None, None, None, 32) == _amr.AMR_OK
+    assert lib.amr_ofdm_demod_acq_host(h, None, F32, 0, SMALL_N, None, 4, None, None, None, 0, None) == _amr.AMR_OK
+    assert lib.amr_ofdm_acquire_host(h, None, F32, 0, SMALL_N, None, None, None) == _amr.AMR_OK
+    assert lib.amr_ofdm_symbols_at_host(h, None, F32, 0, SMALL_N, None, None) == _amr.AMR_OK
+    rng = np.random.default_rng(3)
+    for n in (3, 12 + 3):                                    # S = 0, 1
+        x = rng.normal(0, 0.3, (5, n)).astype(np.float32)
+        pl = plan_for(n, SMALL, 3)
+        assert pl.out_cap == 1
+        assert pl.demod_host(x)[0] == [b""] * 5 and list(pl.demod_host(x)[1]) == [-1] * 5
+        outs, syncs, softs, offs = pl.demod_acq_host(x, soft=True)
+        assert outs == [b""] * 5 and list(syncs) == [-1] * 5 and all(s.size == 0 for s in softs)
+        assert list(offs) == [ac.acquire(r, *SMALL)[0] for r in x]
+
+
+def test_small_scratch_bytes_are_the_estimates():
+    import _amr
+    x = small("f32")[0]
+    lib = _amr.lib()
+    plan_b, acq_b = lib.amr_ofdm_plan_bytes_estimate(SMALL_N, 4, 3, 3), lib.amr_ofdm_acquire_bytes_estimate(SMALL_N, 4, 3, 3)
+    pl = plan_for(SMALL_N, SMALL, 3)
+    # W [Nu][K][2], Y [ms][S][K][2], words [ms][1]: the plan before any call
+    assert pl.scratch_bytes() == 11 * 3 * 16 + 3 * 5 * 3 * 16 + 3 * 4
+    pl.demod_host(x)
+    assert pl.scratch_bytes() == plan_b                      # + x [ms][n] doubles, out [ms][cap], len and sync [ms]
+    assert plan_b == 11 * 3 * 16 + 3 * 5 * 3 * 16 + 3 * 4 + 3 * SMALL_N * 8 + 3 * 4 + 2 * 3 * 8
+    pl.demod_host(x, acquire=True)
+    assert pl.scratch_bytes() == plan_b + acq_b              # + gq [ms][1][L], G and E [ms][L], dhat and off [ms]
+    assert acq_b == 3 * 12 * 8 + 2 * 3 * 12 * 8 + 2 * 3 * 8
+    pl.acquire(x)
+    pl.demod_soft_host(x)
+    assert pl.scratch_bytes() == plan_b + acq_b
+
+
+def test_small_plans_come_and_go():
+    """Create, demodulate twice on the host (the staging allocated, then reused), destroy; a few times over."""
+    x, acq, plain = small("f32")
+    for k in range(3):
+        pl = plan_for(SMALL_N, SMALL, 3)
+        for _ in range(2):
+            assert pl.demod_host(x)[0] == [w[0] for w in plain]
+            assert pl.demod_host(x, acquire=True)[0] == [w[0] for w in acq]
+        del pl

@@ -616,3 +616,123 @@ def test_end_to_end_coded_chain():
     assert sum(o[2:2 + n_cw] != c for o, c in zip(outs, cws)) >= 8             # and most hard codewords are damaged
     rows = [s[16:16 + 8 * n_cw] for s in softs]
     assert fec.ViterbiDecoder().decode_soft_batch(rows) == msgs
+
+
+# ---- 7. the host layer spread shares with ofdm (sym_plan.h), at a small shape ----------------
+# C = 4, spc = 3: L = 12.  n = 5 L + 3: five bits and a tail, 4 decided bits, no whole byte (out_cap 1);
+# n = 21 L + 3: 20 decided bits, 2 bytes (out_cap 3).  The same cases as test_gpu_ofdm_acquire.py's section 4.
+SMALL = (1000, 750.0, [1, 0, 1, 1], 3000)
+SMALL_NS = [5 * 12 + 3, 21 * 12 + 3]
+_small = {}
+
+
+def small(dt, n):
+    """(five rows of a wider array, poisoned behind n; the restatement's acquired and unacquired (bytes, soft,
+    sync, o) of every row), computed once per module."""
+    if (dt, n) not in _small:
+        wide = np.random.default_rng(12 + n).normal(0, 0.3, (5, n + 4))
+        wide = np.round(wide * 8000).astype(np.int16) if dt == "i16" else wide.astype(np.float32)
+        wide[:, n:] = 32767 if dt == "i16" else np.nan
+        x = wide[:, :n]
+        _small[dt, n] = (x, [sp.demod_soft(r, *SMALL) for r in x], [sp.demod_soft(r, *SMALL, acquire_=False) for r in x])
+    return _small[dt, n]
+
+
+@pytest.mark.parametrize("n", SMALL_NS)
+@pytest.mark.parametrize("dt", ["f32", "i16"])
+def test_small_two_batches_of_wider_rows(dt, n):
+    """Five streams through a plan of three (a full batch and a short one), x_stride > n: every host entry."""
+    x, acq, plain = small(dt, n)
+    assert sp.geometry(*SMALL)[:3] == (3, 12, 3) and x.strides[0] == (n + 4) * x.itemsize
+    assert all(len(w[0]) == (n // 12 - 1) // 8 for w in plain)
+    pl = plan_for(n, SMALL, 3)
+    assert pl.out_cap == (n // 12 - 1) // 8 + 1
+    for acquire, want in ((True, acq), (False, plain)):
+        outs, syncs, softs, offs = pl.demod_host(x, soft=True, acquire=acquire)
+        assert outs == [w[0] for w in want] and list(syncs) == [w[2] for w in want], (dt, acquire)
+        assert list(offs) == [w[3] for w in want] and (acquire or not offs.any()), (dt, acquire)
+        assert all(s.dtype == np.int8 and np.array_equal(s, w[1]) for s, w in zip(softs, want)), (dt, acquire)
+        hard = pl.demod_host(x, acquire=acquire)
+        assert hard[0] == outs and np.array_equal(hard[1], syncs) and hard[2] is None and np.array_equal(hard[3], offs)
+    off, P = pl.acquire(x)
+    woff, wP = want_acq(x, SMALL)
+    assert np.array_equal(off, woff) and same_bits(P, wP) and list(off) == [w[3] for w in acq]
+    assert same_bits(pl.symbols_at(x, off), want_Y(x, SMALL, off))
+    assert same_bits(pl.symbols_at(x), want_Y(x, SMALL))
+
+
+@pytest.mark.parametrize("n", SMALL_NS)
+@pytest.mark.parametrize("dt", ["f32", "i16"])
+def test_small_host_soft_rows_are_cut(dt, n):
+    """soft_stride above 8 * out_cap with a sentinel in the slack, out_stride at its minimum: the row is cut at
+    8 * out_len[i] and nothing behind it is written; the offsets are zeros when nothing is acquired."""
+    import _amr
+    x, acq, plain = small(dt, n)
+    x = np.ascontiguousarray(x[:3])
+    pl = plan_for(n, SMALL, 3)
+    lib, cap = _amr.lib(), pl.out_cap
+    stride = max(cap - 1, 1)
+    for acquire, want in ((0, plain), (1, acq)):
+        out, ln, sy = np.zeros((3, stride), np.uint8), np.zeros(3, np.int64), np.zeros(3, np.int64)
+        soft, off = np.full((3, 8 * cap + 5), 77, np.int8), np.full(3, -99, np.int64)
+        _amr.check(lib.amr_dsss_demod_host(pl.handle, _amr.ptr(x), _amr.DTYPES[x.dtype], 3, n, _amr.ptr(out), stride,
+                                           _amr.ptr(ln), _amr.ptr(sy), _amr.ptr(soft), 8 * cap + 5, _amr.ptr(off), acquire))
+        assert [out[i, :ln[i]].tobytes() for i in range(3)] == [w[0] for w in want[:3]]
+        assert list(sy) == [w[2] for w in want[:3]] and list(ln) == [len(w[0]) for w in want[:3]]
+        assert list(off) == [w[3] for w in want[:3]] and (acquire or list(off) == [0, 0, 0])
+        for i in range(3):
+            assert np.array_equal(soft[i, :8 * ln[i]], want[i][1]) and np.all(soft[i, 8 * ln[i]:] == 77), (acquire, i)
+    assert n < 100 or min(ln) > 0                            # the longer capture has bytes to cut at
+
+
+def test_small_empty_batch_and_fewer_than_two_bits():
+    import _amr
+    lib = _amr.lib()
+    n = SMALL_NS[0]
+    pl = plan_for(n, SMALL, 3)
+    h, F32 = pl.handle, _amr.DTYPE_F32
+    for acquire in (0, 1):
+        assert lib.amr_dsss_demod_host(h, None, F32, 0, n, None, 1, None, None, None, 0, None, acquire) == _amr.AMR_OK
+    assert lib.amr_dsss_acquire_host(h, None, F32, 0, n, None, None) == _amr.AMR_OK
+    assert lib.amr_dsss_symbols_at_host(h, None, F32, 0, n, None, None) == _amr.AMR_OK
+    rng = np.random.default_rng(3)
+    for n in (3, 12 + 3):                                    # S = 0, 1
+        x = rng.normal(0, 0.3, (5, n)).astype(np.float32)
+        pl = plan_for(n, SMALL, 3)
+        assert pl.out_cap == 1
+        for acquire in (False, True):
+            outs, syncs, softs, offs = pl.demod_host(x, soft=True, acquire=acquire)
+            assert outs == [b""] * 5 and list(syncs) == [-1] * 5 and all(s.size == 0 for s in softs)
+            assert list(offs) == [sp.acquire(r, *SMALL)[0] if acquire else 0 for r in x]
+
+
+def test_small_scratch_bytes_are_the_estimates():
+    import _amr
+    n = SMALL_NS[0]
+    x = small("f32", n)[0]
+    lib = _amr.lib()
+    plan_b, acq_b = lib.amr_dsss_plan_bytes_estimate(n, 3, 4, 3), lib.amr_dsss_acquire_bytes_estimate(n, 3, 4, 3)
+    pl = plan_for(n, SMALL, 3)
+    # Wc and T [L][2], cs [C], Y [ms][S][2], words [ms][1]: the plan before any call
+    assert pl.scratch_bytes() == 2 * 12 * 16 + 4 * 8 + 3 * 5 * 16 + 3 * 4
+    pl.demod_host(x, acquire=False)
+    assert pl.scratch_bytes() == plan_b                      # + x [ms][n] doubles, out [ms][cap], len and sync [ms]
+    assert plan_b == 2 * 12 * 16 + 4 * 8 + 3 * 5 * 16 + 3 * 4 + 3 * n * 8 + 3 * 1 + 2 * 3 * 8
+    pl.demod_host(x)
+    assert pl.scratch_bytes() == plan_b + acq_b              # + gq [ms][1][L], P [ms][L], off [ms]
+    assert acq_b == 3 * 12 * 8 + 3 * 12 * 8 + 3 * 8
+    pl.acquire(x)
+    pl.demod_host(x, soft=True, acquire=False)
+    assert pl.scratch_bytes() == plan_b + acq_b
+
+
+def test_small_plans_come_and_go():
+    """Create, demodulate twice on the host (the staging allocated, then reused), destroy; a few times over."""
+    n = SMALL_NS[1]
+    x, acq, plain = small("f32", n)
+    for k in range(3):
+        pl = plan_for(n, SMALL, 3)
+        for _ in range(2):
+            assert pl.demod_host(x, acquire=False)[0] == [w[0] for w in plain]
+            assert pl.demod_host(x)[0] == [w[0] for w in acq]
+        del pl
