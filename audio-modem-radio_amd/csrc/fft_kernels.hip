@@ -552,16 +552,24 @@ __global__ __launch_bounds__(kFftThreads) void k_fft_cols_live(double2* zb, doub
       });
 }
 
-// TWG: the row's W_L table is read from global memory (L1 / scalar-cache
-// resident: 4.8 KB shared by every workgroup) instead of LDS, and the position
-// table is 16-bit, so four workgroups fit a CU's LDS instead of three.
-// NT: threads per workgroup.  No stage runs more than 8 * 20 = 160 butterflies
-// at the benchmark lengths, so NT = 192 (three waves) leaves one wave less idle
-// per workgroup, and four workgroups per CU are then three waves per SIMD:
-// 168 VGPRs, no spills (NT = 256 holds 128 and spills).
-template <int PC, int QC, bool TWG, int NT = kFftThreads>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(TWG && PC > 0 ? (NT == kFftThreads ? 4 : 3) : 1))) void k_fft_mid_live(double2* zb, double2* cb, double2* db, FftDesc d, int64_t batch,
+// The row's W_L table is read from global memory (L1 / scalar-cache resident:
+// 4.8 KB shared by every workgroup), not LDS, and the position table is
+// 16-bit, so four workgroups fit a CU's LDS instead of three.
+// Threads per workgroup follow from the radices (fft_mid_live_threads): no
+// stage of a specialised length runs more than 8 * 20 = 160 butterflies, so
+// three waves leave one wave less idle per workgroup, and four workgroups per
+// CU are then three waves per SIMD: 168 VGPRs, no spills (four waves hold 128
+// and spill).  Run-time radices (PC == 0, up to 8 * 25 butterflies) keep four.
+template <int PC, int QC>
+constexpr int fft_mid_live_threads() {
+  static_assert(PC == 0 || (kFftTile * PC <= 192 && kFftTile * QC <= 192),
+                "a specialised middle pass runs each stage on three waves");
+  return PC > 0 ? 192 : kFftThreads;
+}
+template <int PC, int QC>
+__global__ __launch_bounds__((fft_mid_live_threads<PC, QC>())) __attribute__((amdgpu_waves_per_eu(PC > 0 ? 3 : 1))) void k_fft_mid_live(double2* zb, double2* cb, double2* db, FftDesc d, int64_t batch,
                                                              LiveCols lc) {
+  constexpr int NT = fft_mid_live_threads<PC, QC>();
   extern __shared__ __attribute__((aligned(16))) double2 smem[];
   const int tiles = (d.n2 + kFftTile - 1) / kFftTile;
   const int64_t lb = xcd_block();
@@ -580,8 +588,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(TWG && PC > 
                         (size_t)r0 * lc.nd;
   auto y_ld = [&](int t, int j, int m) { return smem[t * S + j + Qp * m]; };
   auto y_st = [&](int t, int j, int m, double2 v) { smem[t * S + j + Qp * m] = v; };
-  // (TWG: never written -- the stage-1 fill is off)
-  double2* twl = TWG ? const_cast<double2*>(f.tw) : twl_of(smem, f);
+  double2* twl = const_cast<double2*>(f.tw);   // (never written: the stage-1 fill is off)
   // column c -> its live index l (>= 0) or ~(dead index d), once per workgroup
   // (the per-element form cost the pass more ALU than its FFT: 12.7 vs 10.9 ms)
   __shared__ int16_t cpos[kFftMaxL];
@@ -596,7 +603,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(TWG && PC > 
   __shared__ int mlive[kFftMaxR];
   __shared__ int nmlive;
   if (threadIdx.x == 0) {
-    const bool prune = lc.prune && P % lc.sps == 0;   // (cpos of m < P: m's own column)
+    const bool prune = P % lc.sps == 0;   // (cpos of m < P: m's own column)
     int k = 0;
     for (int m = 0; m < P; ++m)
       if (!prune || cpos[m] >= 0) mlive[k++] = m;
@@ -610,7 +617,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(TWG && PC > 
         const int pos = cpos[j + Q * q];
         return pos >= 0 ? crow[(unsigned)(t * lc.nl + pos)] : drow[(unsigned)(t * lc.nd + ~pos)];
       },
-      y_st, !TWG);
+      y_st);
   __syncthreads();
   run_stage2<false, PC, QC>(
       f, twl, y_ld,
@@ -862,24 +869,13 @@ hipError_t launch_fft_hilbert_live(double2* zb, double2* cb, double2* db, const 
                      lc)
   AMR_FFT_PQ(d.a, COLSL);
 #undef COLSL
-  // AMR_FFT_MID_TWG=0: the W_L table in LDS (three workgroups per CU instead of four)
-  static const bool twg = [] { const char* e = getenv("AMR_FFT_MID_TWG"); return !(e && e[0] == '0'); }();
-  // three-wave workgroups (specialised lengths, TWG form; AMR_FFT_MID_NT=256:
-  // four waves): solo Hilbert 23.6 -> 22.6 ms, fsk9600 step 33.2 -> 32.5 ms
-  static const bool nt192 = [] { const char* e = getenv("AMR_FFT_MID_NT"); return !e || atoi(e) != 256; }();
-  const size_t sm_mid = twg ? (size_t)kFftTile * d.c.S * sizeof(double2) : fft_smem_bytes(d.c);
-#define MIDL(P, Q)                                                                                              \
-  do {                                                                                                          \
-    if (twg && nt192 && P > 0 && kFftTile * d.c.r1 <= 192 && kFftTile * d.c.r2 <= 192)                          \
-      hipLaunchKernelGGL((k_fft_mid_live<P, Q, true, 192>), dim3(gmid), dim3(192), sm_mid, st, zb, cb, db, d,  \
-                         batch, lc);                                                                            \
-    else if (twg)                                                                                               \
-      hipLaunchKernelGGL((k_fft_mid_live<P, Q, true>), dim3(gmid), dim3(kFftThreads), sm_mid, st, zb, cb, db, \
-                         d, batch, lc);                                                                            \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_fft_mid_live<P, Q, false>), dim3(gmid), dim3(kFftThreads), sm_mid, st, zb, cb, db, \
-                         d, batch, lc);                                                                            \
-  } while (0)
+  // the middle pass holds its kFftTile rows only in LDS (its W_L table is read
+  // from global memory); three-wave workgroups at the specialised lengths:
+  // solo Hilbert 23.6 -> 22.6 ms, fsk9600 step 33.2 -> 32.5 ms
+  const size_t sm_mid = (size_t)kFftTile * d.c.S * sizeof(double2);
+#define MIDL(P, Q)                                                                                               \
+  hipLaunchKernelGGL((k_fft_mid_live<P, Q>), dim3(gmid), dim3(fft_mid_live_threads<P, Q>()), sm_mid, st, zb, cb, db, \
+                     d, batch, lc)
   AMR_FFT_PQ(d.c, MIDL);
 #undef MIDL
 #define FINL(P, Q)                                                                                          \
@@ -970,8 +966,7 @@ static hipError_t fft_set_smem(int bytes) {
       (const void*)k_fft_mid<kHilbert, P, Q>, (const void*)k_fft_mid<kMulTab, P, Q>,
       (const void*)k_fft_rows<false, kStore, P, Q>, (const void*)k_fft_rows<true, kStore, P, Q>,
       (const void*)k_fft_rows<true, kEnvelope, P, Q>, (const void*)k_fft_rows<true, kEnvOut, P, Q>,
-      (const void*)k_fft_cols_live<P, Q>, (const void*)k_fft_mid_live<P, Q, false>,
-      (const void*)k_fft_mid_live<P, Q, true>, (const void*)k_fft_mid_live<P, Q, true, 192>,
+      (const void*)k_fft_cols_live<P, Q>, (const void*)k_fft_mid_live<P, Q>,
       (const void*)k_fft_rows_live<P, Q>};
   for (const void* f : fns) {
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);

@@ -2,7 +2,7 @@
 // points (include/amr.h).  Host code; compiled by hipcc.
 //
 // Pipeline per call (all on the plan's stream):
-//   F1  k_fsk_bandpass          x -> z = f_mark + i f_space           [B][n] c128
+//   F1  k_fsk_bandpass2         x -> z = f_mark + i f_space           [B][n] c128
 //   F2  H[z] = IFFT_n(-i sgn(k) FFT_n(z)) in three passes z -> u -> v -> cmp,
 //       the last forming both envelopes: bit = |a_mark| > |a_space|   [B][n/8] u8
 //   F3  k_fsk_decide + k_sync_pack  cmp bits -> words -> bytes
@@ -371,20 +371,6 @@ struct amr_fsk_plan : PlanCore<AMR_TF_COUNT> {
   bool exact_on = false;
   int32_t* xcount_host = nullptr;   // host-mapped: the count E3 last saw (FskExact count_hint)
   int32_t* xcount_dev = nullptr;    // its device pointer
-  // AMR_FSK_XSTREAM=1 (an A/B, off by default): E0-E3 on a stream of their
-  // own at the device's highest priority, ordered by events after F2 and
-  // before F3, with the full resident grid every batch.  An exact-path
-  // workgroup needs 64 KiB of LDS; from a high-priority queue it takes the
-  // next CU that frees that much ahead of the launches in flight.  Measured
-  // (profiles/r05_fsk_exact_xstream.txt): alone, fsk9600 36.5-36.8 vs
-  // 37.1-37.5 ms/step and a burst of 2048 flagged streams after clean batches
-  // 21.8 vs 393 ms of exact stage; but in the default bench process (the
-  // PSK headline's 21 streams created first) 39.2-39.9 vs 37.3-37.4 ms/step,
-  // two interleaved pairs -- so the plan's own stream stays the default, and
-  // the synchronous host entry sizes the grid from the batch's own count
-  // (count_sync)
-  hipStream_t xstream = nullptr;
-  hipEvent_t ev_f2 = nullptr, ev_x = nullptr;
   // the synchronous host entry (amr_fsk_demod_host) reads E0's count on the
   // host before the envelope kernels: none flagged -> E1-E3 are not launched
   // at all; else E2's grid is sized from this batch's own count
@@ -444,20 +430,16 @@ int64_t fsk_out_staging_bytes(const amr_fsk_plan* pl) {
   return pl->mem.d_out.bytes() + pl->mem.d_len.bytes() + pl->mem.d_sync.bytes() + pl->mem.d_edge.bytes();
 }
 
-// set device, drain both streams, drop the gather gate; then the buffers; then events and the streams
+// set device, drain the stream, drop the gather gate; then the buffers; then events and the stream
 void fsk_plan_free(amr_fsk_plan* pl) {
   if (!pl) return;
   (void)hipSetDevice(pl->device);
   if (pl->stream) (void)hipStreamSynchronize(pl->stream);
-  if (pl->xstream) (void)hipStreamSynchronize(pl->xstream);
   gate_free(pl->gate);
   if (pl->xcount_host) (void)hipHostFree(pl->xcount_host);
   pl->mem = amr_fsk_plan::Mem{};                 // frees every device buffer
   pl->fft.mem = FftPlan::Mem{};
   core_destroy_events(*pl);
-  if (pl->ev_f2) (void)hipEventDestroy(pl->ev_f2);
-  if (pl->ev_x) (void)hipEventDestroy(pl->ev_x);
-  if (pl->xstream) (void)hipStreamDestroy(pl->xstream);
   if (pl->stream) (void)hipStreamDestroy(pl->stream);
   delete pl;
 }
@@ -628,25 +610,10 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
   }
   if (pl->p.lc.on) {
     if (env_out) return fail(AMR_E_INVALID, "live-column plan: envelopes go through a natural-layout plan");
-    // AMR_FSK_SUBBATCH=S (an A/B experiment): the three
-    // passes per sub-batch of S streams (a multiple of 32: the flag words),
-    // so a sub-batch's intermediates could stay in the Infinity Cache
-    // (rounded down to a multiple of 32; below 32: off)
-    static const int64_t sub = env_int("AMR_FSK_SUBBATCH", 32, std::numeric_limits<int64_t>::max(), 0) / 32 * 32;
     const LiveCols& lc = pl->p.lc;
-    const int64_t step = sub > 0 ? sub : B;
-    for (int64_t b0 = 0; b0 < B; b0 += step) {
-      const int64_t nb = std::min(step, B - b0);
-      FftEpi e = env;
-      e.z = env.z + b0 * pl->p.n;
-      e.bits = env.bits + b0 * env.bits_stride;
-      if (e.amb) e.amb += b0;
-      if (e.xflags) e.xflags += b0 / 32;
-      double2* const dd = keeps_z(pl) ? pl->mem.dd.as<double2>() + b0 * (int64_t)lc.nd * lc.n2 : nullptr;
-      HIP_TRY(launch_fft_hilbert_live(pl->mem.z.as<double2>() + b0 * pl->p.n,
-                                      pl->mem.u.as<double2>() + b0 * (int64_t)lc.nl * lc.n2, dd, pl->fft.d, nb, lc, e,
-                                      pl->stream));
-    }
+    HIP_TRY(launch_fft_hilbert_live(pl->mem.z.as<double2>(), pl->mem.u.as<double2>(),
+                                    keeps_z(pl) ? pl->mem.dd.as<double2>() : nullptr, pl->fft.d, B, lc, env,
+                                    pl->stream));
   } else {
     HIP_TRY(fft_hilbert(pl->fft, pl->mem.z.as<double2>(), pl->mem.u.as<double2>(), pl->mem.v.as<double2>(), B, env,
                         pl->stream));
@@ -654,21 +621,10 @@ int run_fsk_f2(amr_fsk_plan* pl, int64_t B, bool env_out) {
   return AMR_OK;
 }
 
-// AMR_FSK_EXACT_LAUNCH=0 (diagnostic A/B only, decisions then NOT exact):
-// F1 / F2 keep their margin work, the E0-E3 launches are skipped (=2: E0 and
-// E3 only, E2 skipped).  Either way F3 then takes every stream's bits from the
-// fast path (run_fsk_back), not from an xbits buffer E2 / E3 never filled.
-int exact_launch_mode() {
-  static const int launch = (int)env_int("AMR_FSK_EXACT_LAUNCH", INT32_MIN, INT32_MAX, 1);
-  return launch;
-}
-
 // The exact path over F2's flagged streams: with keep_z straight from z (F2
 // left it whole), otherwise F1 again over their input x (still resident).
 int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64_t x_stride) {
   if (!pl->exact_on || pl->exact_mode == 0) return AMR_OK;
-  const int launch = exact_launch_mode();
-  if (launch == 0) return AMR_OK;
   FskExact X{};
   X.flags = pl->mem.xflags.as<uint32_t>();
   X.list = pl->mem.xlist.as<int32_t>();
@@ -685,14 +641,8 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
   X.xbits = pl->mem.xbits.as<uint8_t>();
   X.fuse = (int)pf_fuse_on();
   X.lean = X.fuse && pl->x_lean;
-  static const int xcd_pair = env_not_off("AMR_FSK_XCDPAIR");
-  X.xcd_pair = xcd_pair;
-  static const int live_only = env_not_off("AMR_FSK_LIVEONLY");
-  X.live_only = live_only;
   X.count_host = pl->xcount_dev;
-  if (pl->xstream && !pl->count_sync) {
-    X.count_hint = B;                                   // the full resident grid (see xstream)
-  } else if (pl->xcount_host) {
+  if (pl->xcount_host) {
     pl->hint_hist[pl->hint_pos] = *reinterpret_cast<volatile int32_t*>(pl->xcount_host);
     pl->hint_pos = (pl->hint_pos + 1) % amr_fsk_plan::kHintDepth;
     X.count_hint = *std::max_element(pl->hint_hist, pl->hint_hist + amr_fsk_plan::kHintDepth);
@@ -700,14 +650,7 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
     X.count_hint = B;
   }
   hipStream_t st = pl->stream;
-  const bool xs = pl->xstream && !pl->count_sync;
-  if (xs) {
-    HIP_TRY(hipEventRecord(pl->ev_f2, pl->stream));
-    HIP_TRY(hipStreamWaitEvent(pl->xstream, pl->ev_f2, 0));
-    st = pl->xstream;
-  }
-  // the slot on the stream the exact path runs on
-  const int rc = timed(*pl, AMR_TF_EXACT, [&]() -> int {
+  return timed(*pl, AMR_TF_EXACT, [&]() -> int {
     pl->ran_exact = true;
     HIP_TRY(launch_fsk_exact_list(B, X, st));
     if (pl->count_sync) {
@@ -730,15 +673,9 @@ int run_fsk_exact(amr_fsk_plan* pl, const void* d_x, int dtype, int64_t B, int64
       p1.xcount = X.count;
       HIP_TRY(launch_fsk_bandpass(dtype, d_x, x_stride, B, pl->mem.u.as<double>(), pl->mem.z.as<double2>(), p1, pl->f, st));
     }
-    HIP_TRY(launch_fsk_exact_env(B, pl->p, X, st, launch != 2));
+    HIP_TRY(launch_fsk_exact_env(B, pl->p, X, st));
     return AMR_OK;
-  }, st);
-  if (rc) return rc;
-  if (xs) {
-    HIP_TRY(hipEventRecord(pl->ev_x, pl->xstream));
-    HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_x, 0));
-  }
-  return AMR_OK;
+  });
 }
 
 // F1, F2 (and the exact path) on a device-resident batch: x -> cmp (or the envelopes).  Caller holds mu.
@@ -764,10 +701,9 @@ int run_fsk_back(amr_fsk_plan* pl, const DemodIo& io) {
   const int64_t B = io.B;
   hipStream_t st = pl->stream;
   // a flagged stream's bits come from xbits only when this call's E0-E3 wrote
-  // them (exact mode 0 leaves the flag words of an earlier call untouched;
-  // the diagnostic launch modes leave xbits unwritten)
+  // them (exact mode 0 leaves the flag words of an earlier call untouched)
   FskParams p = pl->p;
-  if (!pl->ran_exact || exact_launch_mode() != 1) p.xflags = nullptr;
+  if (!pl->ran_exact) p.xflags = nullptr;
   return timed(*pl, AMR_TF_DECIDE, [&]() -> int {
     HIP_TRY(launch_fsk_decide(pl->mem.cmp.as<uint8_t>(), pl->mem.words.as<uint32_t>(), B, p, st));
     HIP_TRY(gate_wait(pl->gate, st));             // the outputs: after any gather still reading them
@@ -867,8 +803,6 @@ LiveCols plan_live_cols(const FftShape& f, const FskParams& p) {
     seen[(size_t)o] = 1;
   }
   lc.on = 1;
-  static const bool no_prune = !env_not_off("AMR_FFT_PRUNE");
-  lc.prune = !no_prune;
   return lc;
 }
 
@@ -952,9 +886,7 @@ bool fsk_geometry(int64_t n, int64_t sps, int nt, int64_t max_streams, FskGeom& 
     // live layout: keep all of z through F2 (the exact path then needs no F1
     // re-run); the dead tiles' transform and the staged input go to dd
     // (AMR_FSK_KEEPZ=0, an A/B switch: dead tiles in place, the F1 re-run)
-    // (AMR_FSK_F1_FMA=1 makes F1 the contracted form, not scipy's order: the
-    // exact path must then re-run F1 in scipy's order, so no keep_z)
-    static const bool keepz_env = env_not_off("AMR_FSK_KEEPZ") && !env_on("AMR_FSK_F1_FMA");
+    static const bool keepz_env = env_not_off("AMR_FSK_KEEPZ");
     static const bool eager_env = env_on("AMR_FSK_KEEPZ");
     g.keep_z = keepz_env && p.lc.on && (int64_t)p.lc.nd * p.lc.n2 * 2 >= n;
     if (g.keep_z) {
@@ -1270,18 +1202,6 @@ int amr_fsk_plan_create(amr_fsk_plan** out, int device, int64_t n, int64_t sps, 
     pl->p.xbits = pl->mem.xbits.as<uint8_t>();
     pl->n_slots = geo.n_slots;
     pl->slot_doubles = geo.slot_doubles;
-    static const bool xstream_on = env_on("AMR_FSK_XSTREAM");
-    if (xstream_on) {
-      int least = 0, greatest = 0;
-      e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-      if (e == hipSuccess) e = hipStreamCreateWithPriority(&pl->xstream, hipStreamNonBlocking, greatest);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_f2, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_x, hipEventDisableTiming);
-      if (e != hipSuccess) {
-        fsk_plan_free(pl);
-        return fail(AMR_E_HIP, std::string("exact-path stream: ") + hipGetErrorString(e));
-      }
-    }
   }
   {
     FskFftBound fb;

@@ -25,8 +25,6 @@ struct FskExact {
   uint8_t* xbits;          // [B][bits_stride] exact compare bits, F3 reads them for flagged streams
   int fuse;                // LDS-fused transforms (pf_fuse_on)
   int lean;                // ... and every radix hard-coded: k_exact_env_lean
-  int live_only;           // E2b stores only the live samples' envelopes (AMR_FSK_LIVEONLY=0: every sample, A/B)
-  int xcd_pair;            // E2 rows of one stream on one XCD (AMR_FSK_XCDPAIR=0: off, A/B)
   // E2's grid: the persistent loops are correct at any size, so it is sized
   // from the counts the plan's last 8 launches saw (count_hint = their
   // maximum; E3 writes each to count_host, host-mapped) -- a few workgroups
@@ -47,7 +45,6 @@ struct FskExact {
 // then E2 + E3: the flagged streams' exact compare bits in X.xbits.  Every
 // kernel exits at once when nothing is flagged.
 hipError_t launch_fsk_exact_list(int64_t B, const FskExact& X, hipStream_t st);
-hipError_t launch_fsk_exact_env(int64_t B, const FskParams& p, const FskExact& X, hipStream_t st,
-                                bool env = true);
+hipError_t launch_fsk_exact_env(int64_t B, const FskParams& p, const FskExact& X, hipStream_t st);
 
 }  // namespace amr

@@ -68,9 +68,9 @@ __global__ __launch_bounds__(kListThreads) void k_exact_list(const uint32_t* __r
 // on XCD b % 8), rows 2q and 2q + 1 -- the two tones of one stream, each 8
 // bytes of every 16-byte z element -- go to workgroups b and b + 8 of the
 // same XCD, so both halves of z's lines meet in one L2
-__device__ inline int64_t exact_row0(const FskExact& X) {
+__device__ inline int64_t exact_row0() {
   const int G = gridDim.x, b = blockIdx.x;
-  if (!X.xcd_pair || G % 16 != 0) return b;
+  if (G % 16 != 0) return b;
   return (int64_t)(b % 8) * (G / 8) + b / 8;
 }
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kEnvThreads) void k_exact_env(FskParams p, FskExact
   const int64_t n = p.n;
   double* c = X.slots + (size_t)blockIdx.x * X.slot_doubles;
   if (X.fuse && pf_hilbert_fusable(*X.L)) {   // straight from z and back, every transform in LDS tiles
-    for (int64_t r = exact_row0(X); r < 2 * cnt; r += gridDim.x) {
+    for (int64_t r = exact_row0(); r < 2 * cnt; r += gridDim.x) {
       double* zr = X.rows + (size_t)(r >> 1) * 2 * n + (r & 1);
       pf::pf_hilbert_env_x(
           *X.L, X.pool, [=](int64_t i) { return zr[2 * i]; }, [=](int64_t i, double e) { zr[2 * i] = e; }, c, X.fct,
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kEnvThreads) void k_exact_env(FskParams p, FskExact
     }
     return;
   }
-  for (int64_t r = exact_row0(X); r < 2 * cnt; r += gridDim.x) {
+  for (int64_t r = exact_row0(); r < 2 * cnt; r += gridDim.x) {
     double* zr = X.rows + (size_t)(r >> 1) * 2 * n + (r & 1);
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) c[i] = zr[2 * i];
     __syncthreads();
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(4))
   __shared__ pf::Cx lds[2 * kPfTileElems];
   const int64_t cnt = *X.count;
   double* slot = X.slots + (size_t)blockIdx.x * X.slot_doubles;
-  for (int64_t r = exact_row0(X); r < 2 * cnt; r += gridDim.x) {
+  for (int64_t r = exact_row0(); r < 2 * cnt; r += gridDim.x) {
     const ZRow<LIVE> z = zrow<LIVE>(p, X, r);
     // the halfcomplex spectrum parked in natural order (the row's z elements
     // are free once the first group has read them)
@@ -145,10 +145,10 @@ __global__ __launch_bounds__(kEnvThreads) __attribute__((amdgpu_waves_per_eu(4))
   __shared__ pf::Cx lds[2 * kPfTileElems];
   const int64_t cnt = *X.count;
   double* slot = X.slots + (size_t)blockIdx.x * X.slot_doubles;
-  for (int64_t r = exact_row0(X); r < 2 * cnt; r += gridDim.x) {
+  for (int64_t r = exact_row0(); r < 2 * cnt; r += gridDim.x) {
     const ZRow<LIVE> z = zrow<LIVE>(p, X, r);
     auto fget = [=](int j) { return z.zr[2 * (int64_t)j]; };
-    if (LIVE && X.live_only) {   // envelopes in natural order too, the live samples only (E3 reads no others)
+    if constexpr (LIVE) {   // envelopes in natural order too, the live samples only (E3 reads no others)
       const LiveCols lc = z.lc;
       pf::pf_env_row(
           *X.L, X.pool, fget,
@@ -203,7 +203,7 @@ hipError_t launch_fsk_exact_list(int64_t B, const FskExact& X, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_fsk_exact_env(int64_t B, const FskParams& p, const FskExact& X, hipStream_t st, bool env) {
+hipError_t launch_fsk_exact_env(int64_t B, const FskParams& p, const FskExact& X, hipStream_t st) {
   if (B < 1) return hipSuccess;
   // a persistent grid no larger than what is resident at once: a workgroup
   // beyond that would start its rows only after a resident one finished all of
@@ -219,14 +219,11 @@ hipError_t launch_fsk_exact_env(int64_t B, const FskParams& p, const FskExact& X
   static const int res_full = resident((const void*)k_exact_env),
                    res_lean = std::min(resident((const void*)k_exact_rfft<true>), resident((const void*)k_exact_cenv<true>));
   // (FskExact count_hint) two rows per stream, whole XCD rounds of 16, at
-  // least kIdleGrid; AMR_FSK_E2_GRID=G (A/B): at most G workgroups
-  static const int e2_grid = [] { const char* e = std::getenv("AMR_FSK_E2_GRID"); return e ? std::max(1, atoi(e)) : 1 << 30; }();
+  // least kIdleGrid
   constexpr int64_t kIdleGrid = 16;
   const int64_t want = std::max(kIdleGrid, (2 * std::max<int64_t>(X.count_hint, 0) + 15) / 16 * 16);
-  const dim3 gl((unsigned)std::min<int64_t>({X.n_slots, res_lean, e2_grid, want}));
-  if (!env) {
-    // (diagnostic: the envelope kernels skipped)
-  } else if (X.live) {   // the plan guarantees a lean plan (fsk_api.cpp keep_z)
+  const dim3 gl((unsigned)std::min<int64_t>({X.n_slots, res_lean, want}));
+  if (X.live) {   // the plan guarantees a lean plan (fsk_api.cpp keep_z)
     hipLaunchKernelGGL(k_exact_rfft<true>, gl, dim3(kEnvThreads), 0, st, p, X);
     hipLaunchKernelGGL(k_exact_cenv<true>, gl, dim3(kEnvThreads), 0, st, p, X);
   } else if (X.lean) {

@@ -13,7 +13,7 @@
 //   sync on "FB", pack MSB first from idx or 0              modem.py:326-341
 //
 // Kernels:
-//   F1 k_fsk_bandpass  lane = (stream, tone): both band-pass filtfilts, output
+//   F1 k_fsk_bandpass2 lane = (stream, tone): both band-pass filtfilts, output
 //                      packed as the complex signal z = f_mark + i f_space,
 //                      stream-major.
 //   F2 (fft_kernels.hip) H[z] = IFFT(-i sgn(k) FFT(z)) = H[f_mark] + i H[f_space]
@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "amr_internal.h"
+#include "env_switch.h"
 #include "odd_ext.h"
 #include "split_bound.h"
 #include "split_chain.h"
@@ -53,22 +54,10 @@ namespace amr {
 // antisymmetric numerator b6 = -b0, b4 = -b2 bit for bit: x*b6 IS -(x*b0),
 // so z5 = x*b6 - y*a6 is (-(x*b0)) - y*a6 = -(x*b0) - y*a6 exactly, and
 // z4 + x*b4 is z4 - x*b2: two products per step instead of four (17 FP64).
-// MODE 2 (AMR_FSK_F1_FMA=1, a timing A/B only): the round-3 contracted form
-// (10 FMAs per step), whose f is NOT scipy's -- its rounding grows with the
-// band-pass filter's noise gain (~1e-10 of the peak at 1200 Bd), beyond the
-// exact path's margin.
 template <int MODE>
 __device__ __forceinline__ double fsk_step(double (&z)[6], const double (&b)[7], const double (&a)[7], double x) {
-  if constexpr (MODE == 2) {
-    const double y = __builtin_fma(b[0], x, z[0]);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const double zin = ((i & 1) == 0) ? z[i + 1] : __builtin_fma(x, b[i + 1], z[i + 1]);
-      z[i] = __builtin_fma(-y, a[i + 1], zin);
-    }
-    z[5] = __builtin_fma(-y, a[6], x * b[6]);
-    return y;
-  } else if constexpr (MODE == 3) {
+  static_assert(MODE == 0 || MODE == 1 || MODE == 3, "fsk_step: scipy's order only");
+  if constexpr (MODE == 3) {
     const double xb0 = x * b[0], xb2 = x * b[2];
     const double y = z[0] + xb0;
     z[0] = z[1] - y * a[1];
@@ -134,25 +123,6 @@ template <> struct PeakT<int16_t> {
 };
 
 
-constexpr int kFskTile = 64;          // samples per input tile (and per checkpoint)
-
-// F1 scratch, per wave: checkpoints ck[tile][6 states][64 lanes] doubles, then
-// the forward outputs of the tail (the last n % 64 samples and the right
-// extension) tl[j][64 lanes].
-__host__ __device__ inline int64_t fsk_tail_len(int64_t n, int pad) { return n % kFskTile + pad; }
-__host__ __device__ inline int64_t fsk_scratch_doubles_per_wave(int64_t n, int pad) {
-  return ((n / kFskTile) * 6 + fsk_tail_len(n, pad)) * 64;
-}
-
-// F1.  wave = 32 streams x 2 tones (lane = 2*stream + tone), checkpointed
-// filtfilt: the forward pass keeps only each 64-sample tile's starting state
-// (and the short tail's outputs); the backward pass walks the tiles top-down,
-// re-runs the forward recursion of a tile from its checkpoint (bit-identical
-// outputs, kept in LDS), then runs the backward recursion over them.  HBM
-// traffic per sample: x twice and z once, instead of also writing and
-// re-reading the forward outputs (DESIGN.md §FSK).  Input tiles are loaded 16 B
-// per lane and transposed through LDS; outputs are written back into the same
-// LDS slots and stored as 1 KiB rows of z (stream-major f_mark + i f_space).
 // LIVE: z in the live-column layout (amr_internal.h LiveCols), else [s][i].
 template <bool LIVE>
 __device__ __forceinline__ int64_t fsk_zoff(const FskParams& p, int64_t i) {
@@ -160,185 +130,49 @@ __device__ __forceinline__ int64_t fsk_zoff(const FskParams& p, int64_t i) {
   else return i;
 }
 
-template <typename T, int ZO, bool LIVE, bool AMB = false>
-__global__ __launch_bounds__(64) void k_fsk_bandpass(const void* xv, int64_t x_stride, int64_t n_streams,
-                                                     double* __restrict__ scratch, double2* __restrict__ z,
-                                                     FskParams p, FskIir f) {
-  constexpr int RB = kFskTile * (int)sizeof(T);     // bytes per stream row per tile
-  constexpr int PITCH = RB + 16;
-  constexpr int LPR = RB / 16;                      // lanes per row in a load
-  constexpr int RPI = 64 / LPR;                     // rows per load instruction
-  constexpr int NI = 32 / RPI;                      // load instructions per tile
-  constexpr int YP = 66;                            // yb pitch (doubles): 16-B slot (33 l + row) % 16
-  __shared__ __attribute__((aligned(16))) uint8_t tin[2][32][PITCH];
-  __shared__ __attribute__((aligned(16))) double yb[kFskTile][YP];   // [sample][lane]
-  const int lane = threadIdx.x;
-  const int tone = lane & 1, sl = lane >> 1;
-  const int64_t w = blockIdx.x;
-  const int64_t s = w * 32 + sl;
-  const int64_t last = n_streams - 1;
-  const T* __restrict__ xall = reinterpret_cast<const T*>(xv);
-  const T* __restrict__ x = xall + (s < last ? s : last) * x_stride;
-  const int64_t n = p.n;
-  const int pad = p.pad;
-  const int64_t n_tiles = n / kFskTile;
-  const int64_t n_main = n_tiles * kFskTile;
-  double* __restrict__ ck = scratch + (size_t)w * fsk_scratch_doubles_per_wave(n, pad) + lane;
-  double* __restrict__ tl = ck + (size_t)n_tiles * 6 * 64;
-  double b[7], a[7], zs[6];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) { b[i] = f.b[tone][i]; a[i] = f.a[tone][i]; }
-
-  const int rsub = lane / LPR, cb = (lane % LPR) * 16;
-  const uint8_t* rowp[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int64_t rs = w * 32 + RPI * i + rsub;
-    rowp[i] = reinterpret_cast<const uint8_t*>(xall + (rs < last ? rs : last) * x_stride) + cb;
-  }
-  v4u r[NI];
-  auto fetch = [&](int64_t t) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) r[i] = *reinterpret_cast<const v4u*>(rowp[i] + t * RB);
-  };
-  auto deposit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) *reinterpret_cast<v4u*>(&tin[buf][RPI * i + rsub][cb]) = r[i];
-  };
-  uint32_t pk_hi = 0, pk_lo = 0;   // AMB: the input peak (PeakT)
-  // forward steps over tile `buf`; emit(k, y)
-  auto run_tile = [&](int buf, auto emit, bool det = false) {
-    constexpr int PER = 16 / (int)sizeof(T);
-#pragma unroll
-    for (int k = 0; k < kFskTile; k += PER) {
-      const v4u v = *reinterpret_cast<const v4u*>(&tin[buf][sl][k * sizeof(T)]);
-      if (AMB && det) PeakT<T>::acc(v, pk_hi, pk_lo);
-      T xs[PER];
-      __builtin_memcpy(xs, &v, 16);
-#pragma unroll
-      for (int u = 0; u < PER; ++u) emit(k + u, fsk_step<ZO>(zs, b, a, In<T>::cvt(xs[u])));
-    }
-  };
-
-  // ---- forward pass: checkpoints only ------------------------------------
-  const OddExt<T> ox(x, p.edge, s < last ? s : last, n, pad);
-  const double e0 = ox.left(0);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) zs[i] = f.zi[tone][i] * e0;
-  for (int j = 0; j < pad; ++j) (void)fsk_step<ZO>(zs, b, a, ox.left(j));   // trimmed later
-  if (n_tiles > 0) {
-    fetch(0);
-    deposit(0);
-    __syncthreads();
-    for (int64_t t = 0; t < n_tiles; ++t) {
-      const int cur = (int)(t & 1);
-      fetch(t + 1 < n_tiles ? t + 1 : t);                 // unconditional (clamped) prefetch
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ck[((size_t)t * 6 + i) * 64] = zs[i];
-      run_tile(cur, [](int, double) {}, true);
-      __builtin_amdgcn_sched_barrier(0);
-      deposit(cur ^ 1);
-      __syncthreads();
-    }
-  }
-  for (int64_t i = n_main; i < n; ++i) {
-    if constexpr (AMB) PeakT<T>::one(x[i], pk_hi, pk_lo);
-    tl[(size_t)(i - n_main) * 64] = fsk_step<ZO>(zs, b, a, In<T>::cvt(x[i]));
-  }
-  if constexpr (AMB) {
-    if (tone == 0 && s < n_streams)
-      p.amb[s] = p.force_exact ? __builtin_inf() : amb_scale(ox.peak_with_tab(PeakT<T>::peak(pk_hi, pk_lo)), p.tau);
-    if (lane == 0) p.xflags[w] = 0u;
-  }
-  double ylast = 0.0;
-  for (int j = 0; j < pad; ++j) {
-    ylast = fsk_step<ZO>(zs, b, a, ox.right(j));
-    tl[(size_t)(n - n_main + j) * 64] = ylast;
-  }
-  __threadfence();
-
-  // ---- backward pass --------------------------------------------------------
-#pragma unroll
-  for (int i = 0; i < 6; ++i) zs[i] = f.zi[tone][i] * ylast;
-  for (int64_t j = n - n_main + pad - 1; j >= n - n_main; --j) (void)fsk_step<ZO>(zs, b, a, tl[(size_t)j * 64]);
-  double* __restrict__ zd = reinterpret_cast<double*>(z);
-  for (int64_t i = n - 1; i >= n_main; --i) {          // tail outputs, one sample at a time
-    const double y = fsk_step<ZO>(zs, b, a, tl[(size_t)(i - n_main) * 64]);
-    if (s < n_streams) zd[((size_t)s * n + fsk_zoff<LIVE>(p, i)) * 2 + tone] = y;
-  }
-  if (n_tiles > 0) {
-    double zf[6], zb[6];
-    fetch(n_tiles - 1);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) zf[i] = ck[((size_t)(n_tiles - 1) * 6 + i) * 64];
-    for (int64_t t = n_tiles - 1; t >= 0; --t) {
-      deposit(0);
-      __syncthreads();
-      const int64_t tp = t > 0 ? t - 1 : 0;
-      fetch(tp);                                            // next (lower) tile, and its checkpoint
-#pragma unroll
-      for (int i = 0; i < 6; ++i) zb[i] = ck[((size_t)tp * 6 + i) * 64];
-      __builtin_amdgcn_sched_barrier(0);
-      // forward recursion of tile t from its checkpoint -> yb
-      double zsave[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) { zsave[i] = zs[i]; zs[i] = zf[i]; }
-      run_tile(0, [&](int k, double y) { yb[k][lane] = y; });
-#pragma unroll
-      for (int i = 0; i < 6; ++i) { zs[i] = zsave[i]; zf[i] = zb[i]; }
-      // backward recursion over it, outputs in place
-#pragma unroll 8
-      for (int k = kFskTile - 1; k >= 0; --k) yb[k][lane] = fsk_step<ZO>(zs, b, a, yb[k][lane]);
-      __syncthreads();
-      // 32 rows x 64 samples of z, one 1 KiB row per store instruction
-      const int64_t zo = fsk_zoff<LIVE>(p, t * kFskTile + lane);
-#pragma unroll 4
-      for (int row = 0; row < 32; ++row) {
-        const int64_t so = w * 32 + row;
-        const double2 v = *reinterpret_cast<const double2*>(&yb[lane][2 * row]);
-        if (so < n_streams) z[(size_t)so * n + zo] = v;
-      }
-      __syncthreads();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-// F1, role-split form (the default).  Workgroup = two waves over the same 32
-// streams x 2 tones: wave 0 runs every forward recursion, wave 1 every
-// backward one, so the checkpointed filtfilt's second half overlaps:
+// F1.  Workgroup = two waves over the same 32 streams x 2 tones (lane =
+// 2*stream + tone), a checkpointed filtfilt split by role: wave 0 runs every
+// forward recursion, wave 1 every backward one, so the second half overlaps:
 //   phase 1  wave 0: forward pass keeping each 32-sample tile's starting
 //            state (global scratch) and the tail's forward outputs (LDS)
 //   phase 1b wave 1: backward recursion over the right extension and the
 //            tail (outputs of the last n % 32 samples straight to z)
-//   phase 2  iteration i: wave 0 stores tile T+1-i (1 KiB rows of z from
-//            yb[i & 1], run backward by wave 1 in iteration i-1), then re-runs
-//            tile T-1-i forward from its checkpoint into yb[i & 1], while wave 1
-//            runs tile T-i backward in yb[(i-1) & 1]; one block barrier per
-//            iteration
-// 1024 waves fill the 1024 SIMDs at B = 16384 (the one-wave form: 512), and
-// phase 2 costs one recursion per sample instead of two.  Arithmetic and
-// order per recursion are those of k_fsk_bandpass (same outputs).
-// AMR_FSK_TILE=64 (an A/B; default 32): samples per tile.  A tile of 64 held
-// 77 KB of LDS per workgroup (two re-run buffers of 64 samples x 64 lanes),
-// so two F1 workgroups filled a CU's LDS and no FFT-pass workgroup could sit
-// beside them; 32 halves that at twice the checkpoints (3 B per sample):
-// fsk9600 37.03-37.16 -> 34.68-34.79 ms/step, and 16 (four times the
-// checkpoints) measured 35.75-35.77 against 32's 35.38-35.60 on another box
-// (profiles/r05_fsk_f1_tile.txt); AMR_FSK_TILE=40 (f32 / f64; the generic
-// load / store mapping below) measured 35.11-35.29 vs 34.55-34.61 ms/step
+//   phase 2  iteration i: wave 0 re-runs tile T-1-i forward from its
+//            checkpoint (bit-identical outputs) into yb[i & 1], while wave 1
+//            runs tile T-i backward in yb[(i-1) & 1] and stores it right away
+//            as 1 KiB rows of z (the stores ride on the wave with less
+//            arithmetic per tile); one block barrier per iteration
+// HBM traffic per sample: x twice and z once, instead of also writing and
+// re-reading the forward outputs (DESIGN.md §FSK).  Input tiles are loaded 16 B
+// per lane and transposed through LDS.  1024 waves fill the 1024 SIMDs at
+// B = 16384, and phase 2 costs one recursion per sample instead of two.
+// The tile is 32 samples: 64 held 77 KB of LDS per workgroup (two re-run
+// buffers of 64 samples x 64 lanes), so two F1 workgroups filled a CU's LDS
+// and no FFT-pass workgroup could sit beside them; 32 halves that at twice
+// the checkpoints (3 B per sample): fsk9600 37.03-37.16 -> 34.68-34.79
+// ms/step, 16 (four times the checkpoints) measured 35.75-35.77 against 32's
+// 35.38-35.60 on another box, and 40 measured 35.11-35.29 vs 34.55-34.61
+// (profiles/r05_fsk_f1_tile.txt).
 constexpr int kFsk2Tile = 32;
-constexpr int kFsk2TileMin = 32;
-__host__ __device__ inline int64_t fsk2_scratch_doubles_per_group(int64_t n, int tl = kFsk2Tile) {
-  return (n / tl) * 6 * 64;
+static_assert(64 % kFsk2Tile == 0, "store_tile: whole rows of a tile per 64-lane store");
+__host__ __device__ inline int64_t fsk2_scratch_doubles_per_group(int64_t n) { return (n / kFsk2Tile) * 6 * 64; }
+// What a plan reserves per group of 32 streams beyond that: the scratch of a
+// one-wave F1 with 64-sample tiles (a checkpoint per tile, plus the forward
+// outputs of the last n % 64 samples and the right extension).  No kernel
+// uses it; it is the larger term for short streams (every n < 32, where F1
+// keeps no checkpoint at all), and the plans' scratch totals are pinned to the
+// byte (amr_fsk_plan_scratch_bytes, amr_fsk_plan_bytes_estimate, the plan
+// cache's eviction): shrinking the reservation is a footprint change for a
+// change of its own.
+inline int64_t fsk_scratch_reserve_doubles_per_group(int64_t n, int pad) {
+  return ((n / 64) * 6 + n % 64 + pad) * 64;
 }
 
-template <typename T, int ZO, bool LIVE, bool W1S, bool AMB = false, int TLT = kFsk2Tile>
+template <typename T, int ZO, bool LIVE, bool AMB = false>
 __global__ __launch_bounds__(128) void k_fsk_bandpass2(const void* xv, int64_t x_stride, int64_t n_streams,
                                                        double* __restrict__ scratch, double2* __restrict__ z,
                                                        FskParams p, FskIir f) {
-  constexpr int TL = TLT;
+  constexpr int TL = kFsk2Tile;
   constexpr int RB = TL * (int)sizeof(T);           // bytes per stream row per tile
   constexpr int PITCH = RB + 16;
   constexpr int LPR = RB / 16;                      // 16-B segments per stream row
@@ -377,7 +211,7 @@ __global__ __launch_bounds__(128) void k_fsk_bandpass2(const void* xv, int64_t x
   const int64_t n_tiles = n / TL;
   const int64_t n_main = n_tiles * TL;
   const int64_t ntail = n - n_main + pad;            // <= TL - 1 + 21 <= YR
-  double* __restrict__ ck = scratch + (size_t)w * fsk2_scratch_doubles_per_group(n, TL) + lane;
+  double* __restrict__ ck = scratch + (size_t)w * fsk2_scratch_doubles_per_group(n) + lane;
   double b[7], a[7], zs[6];
 #pragma unroll
   for (int i = 0; i < 7; ++i) { b[i] = f.b[tone][i]; a[i] = f.a[tone][i]; }
@@ -486,32 +320,19 @@ __global__ __launch_bounds__(128) void k_fsk_bandpass2(const void* xv, int64_t x
   // RPS rows per 1-KiB store instruction, lane -> (row, sample)
   auto store_tile = [&](int bb, int64_t tz) {
     const double (*buf)[YP] = &yb[bb * TL];
-    if constexpr (64 % TL == 0) {
-      constexpr int RPS = 64 / TL;
-      const int sub = lane / TL, k = lane % TL;
-      const int64_t zo = fsk_zoff<LIVE>(p, tz * TL + k);
+    constexpr int RPS = 64 / TL;
+    const int sub = lane / TL, k = lane % TL;
+    const int64_t zo = fsk_zoff<LIVE>(p, tz * TL + k);
 #pragma unroll 4
-      for (int row = 0; row < 32; row += RPS) {
-        const int rr = row + sub;
-        const int64_t so = w * 32 + rr;
-        const double2 v = *reinterpret_cast<const double2*>(&buf[k][2 * rr]);
-        if (so < ns) z[(size_t)so * n + zo] = v;
-      }
-    } else {
-      // lanes k < TL, one row of TL samples per store instruction
-      const int k = lane < TL ? lane : TL - 1;
-      const int64_t zo = fsk_zoff<LIVE>(p, tz * TL + k);
-#pragma unroll 4
-      for (int row = 0; row < 32; ++row) {
-        const int64_t so = w * 32 + row;
-        const double2 v = *reinterpret_cast<const double2*>(&buf[k][2 * row]);
-        if (lane < TL && so < ns) z[(size_t)so * n + zo] = v;
-      }
+    for (int row = 0; row < 32; row += RPS) {
+      const int rr = row + sub;
+      const int64_t so = w * 32 + rr;
+      const double2 v = *reinterpret_cast<const double2*>(&buf[k][2 * rr]);
+      if (so < ns) z[(size_t)so * n + zo] = v;
     }
   };
-  // ---- phase 2: wave 0 re-forwards tile T-1-i while wave 1 runs tile T-i backward
-  // (W1S: and stores it right away -- the stores ride on the wave with less
-  // arithmetic per tile; otherwise wave 0 stores it an iteration later)
+  // ---- phase 2: wave 0 re-forwards tile T-1-i while wave 1 runs tile T-i
+  // backward and stores it right away
   if (role == 0) {
     // tiles top-down; inputs and checkpoints two tiles ahead
     double c0[6], c1[6];
@@ -528,7 +349,6 @@ __global__ __launch_bounds__(128) void k_fsk_bandpass2(const void* xv, int64_t x
     }
     auto refwd = [&](v4u (&r)[NI], double (&c)[6], int64_t it) {
       const int64_t t = n_tiles - 1 - it;
-      if (!W1S && it >= 2) store_tile((int)(it & 1), t + 2);   // done by wave 1 in iteration it-1
       if (t >= 0) {
         deposit(r);
 #pragma unroll
@@ -547,14 +367,13 @@ __global__ __launch_bounds__(128) void k_fsk_bandpass2(const void* xv, int64_t x
       refwd(r1, c1, it + 1);
     }
     if (it <= n_tiles) refwd(r0, c0, it);
-    if (!W1S && n_tiles >= 1) store_tile((int)((n_tiles - 1) & 1), 0);   // wave 1's last tile
   } else {
     for (int64_t it = 0; it <= n_tiles; ++it) {
       if (it >= 1) {                                     // tile n_tiles - it, re-run forward by wave 0
         double (*buf)[YP] = &yb[((it - 1) & 1) * TL];
 #pragma unroll 8
         for (int k = TL - 1; k >= 0; --k) buf[k][lane] = fsk_step<ZO>(zs, b, a, buf[k][lane]);
-        if constexpr (W1S) store_tile((int)((it - 1) & 1), n_tiles - it);
+        store_tile((int)((it - 1) & 1), n_tiles - it);
       }
       __syncthreads();
     }
@@ -934,27 +753,20 @@ __global__ __launch_bounds__(256) void k_fsk_decide_bits(const uint8_t* __restri
 }
 
 int64_t fsk_bandpass_scratch_bytes(int64_t n_streams, int64_t n, int pad) {
-  const int64_t per = std::max(fsk_scratch_doubles_per_wave(n, pad), fsk2_scratch_doubles_per_group(n, kFsk2TileMin));
+  const int64_t per = std::max(fsk_scratch_reserve_doubles_per_group(n, pad), fsk2_scratch_doubles_per_group(n));
   return ((n_streams + 31) / 32) * per * (int64_t)sizeof(double);
-}
-
-static bool fsk_one_wave() {
-  static const bool v = [] { const char* e = getenv("AMR_FSK_BP1"); return e && e[0] == '1'; }();
-  return v;
 }
 
 // fsk_step's MODE: 3 when the odd taps are zero and the numerator is
 // antisymmetric (always, for butter(3, band)), 1 with zero odd taps only,
-// else 0; AMR_FSK_ZO=0 forces 0; AMR_FSK_F1_FMA=1 the contracted form (2)
-static int fsk_step_mode(const FskIir& f, bool allow_fma) {
-  static const bool off = [] { const char* e = getenv("AMR_FSK_ZO"); return e && e[0] == '0'; }();
-  static const bool fma = [] { const char* e = getenv("AMR_FSK_F1_FMA"); return e && e[0] == '1'; }();
+// else 0; AMR_FSK_ZO=0 forces 0
+static int fsk_step_mode(const FskIir& f) {
+  static const bool off = !env_not_off("AMR_FSK_ZO");
   bool zo = !off, anti = true;
   for (int t = 0; t < 2; ++t) {
     if (f.b[t][1] != 0.0 || f.b[t][3] != 0.0 || f.b[t][5] != 0.0) zo = false;
     if (f.b[t][6] != -f.b[t][0] || f.b[t][4] != -f.b[t][2]) anti = false;
   }
-  if (fma && allow_fma && zo) return 2;
   if (zo && anti) return 3;
   return zo ? 1 : 0;
 }
@@ -963,44 +775,16 @@ template <int ZO, bool LIVE>
 static hipError_t launch_fsk_bandpass_t(int dtype, const void* x, int64_t x_stride, int64_t n_streams, double* s1,
                                         double2* z, const FskParams& p, const FskIir& f, hipStream_t st) {
   const unsigned grid = (unsigned)((n_streams + 31) / 32);
-  if (!fsk_one_wave() || p.xlist) {
-    // AMR_FSK_W1S=0: wave 0 stores z (the round-2 schedule)
-    static const bool w1s = [] { const char* e = getenv("AMR_FSK_W1S"); return !(e && e[0] == '0'); }();
-    static const int tile_env = [] { const char* e = getenv("AMR_FSK_TILE"); return e ? atoi(e) : 0; }();
-    const bool t64 = tile_env == 64, t40 = tile_env == 40 && dtype != kI16;
-#define BP2(T, S, D)                                                                                                 \
-  do {                                                                                                               \
-    if (t64)                                                                                                         \
-      hipLaunchKernelGGL((k_fsk_bandpass2<T, ZO, LIVE, S, D, 64>), dim3(grid), dim3(128), 0, st, x, x_stride,         \
-                         n_streams, s1, z, p, f);                                                                    \
-    else if (t40 && sizeof(T) != 2)                                                                                  \
-      hipLaunchKernelGGL((k_fsk_bandpass2<T, ZO, LIVE, S, D, (sizeof(T) == 2 ? 32 : 40)>), dim3(grid), dim3(128), 0,  \
-                         st, x, x_stride, n_streams, s1, z, p, f);                                                   \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_fsk_bandpass2<T, ZO, LIVE, S, D>), dim3(grid), dim3(128), 0, st, x, x_stride, n_streams,  \
-                         s1, z, p, f);                                                                               \
-  } while (0)
-#define BP2D(T) do { if (p.amb) { if (w1s) BP2(T, true, true); else BP2(T, false, true); } else if (w1s) BP2(T, true, false); else BP2(T, false, false); } while (0)
-    switch (dtype) {
-      case kF32: BP2D(float); break;
-      case kF64: BP2D(double); break;
-      case kI16: BP2D(int16_t); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef BP2D
-#undef BP2
-    return hipGetLastError();
-  }
-#define BP1(T, A) hipLaunchKernelGGL((k_fsk_bandpass<T, ZO, LIVE, A>), dim3(grid), dim3(64), 0, st, x, x_stride, n_streams, s1, z, p, f)
-#define BP1D(T) do { if (p.amb) BP1(T, true); else BP1(T, false); } while (0)
+#define BP2(T, D) hipLaunchKernelGGL((k_fsk_bandpass2<T, ZO, LIVE, D>), dim3(grid), dim3(128), 0, st, x, x_stride, n_streams, s1, z, p, f)
+#define BP2D(T) do { if (p.amb) BP2(T, true); else BP2(T, false); } while (0)
   switch (dtype) {
-    case kF32: BP1D(float); break;
-    case kF64: BP1D(double); break;
-    case kI16: BP1D(int16_t); break;
+    case kF32: BP2D(float); break;
+    case kF64: BP2D(double); break;
+    case kI16: BP2D(int16_t); break;
     default: return hipErrorInvalidValue;
   }
-#undef BP1D
-#undef BP1
+#undef BP2D
+#undef BP2
   return hipGetLastError();
 }
 
@@ -1008,11 +792,10 @@ static hipError_t launch_fsk_bandpass_t(int dtype, const void* x, int64_t x_stri
 // the chunk's first stream); p.lc.on selects the live-column layout
 hipError_t launch_fsk_bandpass(int dtype, const void* x, int64_t x_stride, int64_t n_streams, double* s1, double2* z,
                                const FskParams& p, const FskIir& f, hipStream_t st) {
-  const int mode = fsk_step_mode(f, !p.xlist);   // the exact path: scipy's order always
+  const int mode = fsk_step_mode(f);
 #define BPM(M) (p.lc.on ? launch_fsk_bandpass_t<M, true>(dtype, x, x_stride, n_streams, s1, z, p, f, st) \
                         : launch_fsk_bandpass_t<M, false>(dtype, x, x_stride, n_streams, s1, z, p, f, st))
   if (mode == 3) return BPM(3);
-  if (mode == 2) return BPM(2);
   return mode == 1 ? BPM(1) : BPM(0);
 #undef BPM
 }
@@ -1029,7 +812,7 @@ hipError_t launch_fsk_split(int dtype, const void* x, int64_t x_stride, int64_t 
     e = hipMemsetAsync(sp.bnd, 0, (size_t)B * 2 * 8 * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
   }
-  const int mode = fsk_step_mode(f, false);
+  const int mode = fsk_step_mode(f);
   if (sp.strict) {
     // the strict bound covers the convolution starts and scipy's step order only
     if (!sp.conv || !sp.rows.sc || !sp.bnd || sp.L % kStrictBlk != 0 || !sp.sb[0].kabs || !sp.sb[1].kabs)
@@ -1047,9 +830,9 @@ hipError_t launch_fsk_decide(const uint8_t* cmp, uint32_t* words, int64_t n_stre
                              hipStream_t st) {
   if (p.n_words < 1 || p.n_bits < 1) return hipSuccess;
   // AMR_FSK_DECIDE_GLOBAL=1: the global-memory form at every length (tests)
-  static const bool force_global = [] { const char* e = getenv("AMR_FSK_DECIDE_GLOBAL"); return e && e[0] == '1'; }();
+  static const bool force_global = env_on("AMR_FSK_DECIDE_GLOBAL");
   // a few streams: thread per bit (k_fsk_decide_bits); AMR_FSK_DECIDE_BITS=0 keeps the per-stream form
-  static const bool bits_off = [] { const char* e = getenv("AMR_FSK_DECIDE_BITS"); return e && e[0] == '0'; }();
+  static const bool bits_off = !env_not_off("AMR_FSK_DECIDE_BITS");
   if (n_streams <= 64 && !bits_off && !force_global) {
     hipLaunchKernelGGL(k_fsk_decide_bits, dim3((unsigned)((p.n_bits + 255) / 256), (unsigned)n_streams), dim3(256), 0,
                        st, cmp, words, p);

@@ -33,13 +33,13 @@ void core_clear_used(PlanCore<N>& c) {
   for (bool& u : c.ev_used) u = false;
 }
 
-// start (which = 0) or end (1) of `slot`, on `st` (null: the plan's stream);
+// start (which = 0) or end (1) of `slot`, on the plan's stream;
 // kNoSlot: nothing (a stage that runs inside another's slot)
 constexpr int kNoSlot = -1;
 template <int N>
-hipError_t core_mark(PlanCore<N>& c, int slot, int which, hipStream_t st = nullptr) {
+hipError_t core_mark(PlanCore<N>& c, int slot, int which) {
   if (slot == kNoSlot) return hipSuccess;
-  if (!st) st = c.stream;
+  const hipStream_t st = c.stream;
   if (which == 1 && slot < c.n_sync_names) {
     static const bool sync_each = env_on("AMR_SYNC_EACH_KERNEL");
     if (sync_each) {
@@ -58,10 +58,10 @@ hipError_t core_mark(PlanCore<N>& c, int slot, int which, hipStream_t st = nullp
 // `body` (int(), an AMR_* code) between the slot's two marks; a failure
 // returns at once, the slot's end unrecorded
 template <int N, class F>
-int timed(PlanCore<N>& c, int slot, F&& body, hipStream_t st = nullptr) {
-  HIP_TRY(core_mark(c, slot, 0, st));
+int timed(PlanCore<N>& c, int slot, F&& body) {
+  HIP_TRY(core_mark(c, slot, 0));
   if (int rc = body()) return rc;
-  HIP_TRY(core_mark(c, slot, 1, st));
+  HIP_TRY(core_mark(c, slot, 1));
   return AMR_OK;
 }
 // the same for one launch (a hipError_t expression), in HIP_TRY's form

@@ -3,7 +3,7 @@
 # "ENV=.. ENV2=..|bench args" runs REPS times, interleaved, each under its own
 # time limit; the JSON lines go to gpurun_out/ab_<TAG>_<rep>_<i>.json and a
 # summary (ms/step, sustained, dominant kernel's solo ms) is printed.
-#   VARIANTS='AMR_FFT_MID_NT=256|--workload fsk9600;|--workload fsk9600' REPS=2 TAG=mid bash scripts/ab_rep.sh
+#   VARIANTS='AMR_FSK_KEEPZ=0|--workload fsk9600;|--workload fsk9600' REPS=2 TAG=keepz bash scripts/ab_rep.sh
 # Optional PYTEST='-k variants tests/test_gpu_fsk.py': a parity run first.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -521,16 +521,16 @@ def test_fsk_live_async_host_entry():
     assert got == [oracle.fsk_demodulate(r, 9600, 12000.0, 24000.0) for r in x]
 
 
-@pytest.mark.parametrize("env", [{"AMR_FFT_MID_TWG": "0"}, {"AMR_FFT_PRUNE": "0"}, {"AMR_FSK_W1S": "0"},
-                                 {"AMR_FSK_BP1": "1"}, {"AMR_FFT_MID_NT": "256"}, {"AMR_FSK_DECIDE_BITS": "0"},
-                                 {"AMR_FSK_SPLIT": "1"}, {"AMR_FSK_TILE": "40"}, {"AMR_FSK_TILE": "64"},
-                                 {"AMR_FSK_KEEPZ": "0"}, {"AMR_FSK_SPLIT": "1", "AMR_FSK_SPLIT_CONV": "0"}],
-                         ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("env", [{}, {"AMR_FSK_DECIDE_BITS": "0"}, {"AMR_FSK_SPLIT": "1"}, {"AMR_FSK_KEEPZ": "0"},
+                                 {"AMR_FSK_SPLIT": "1", "AMR_FSK_SPLIT_CONV": "0"}],
+                         ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()) or "serial-F1")
 def test_fsk_live_kernel_variants(tmp_path, env):
-    """Every kernel variant of the live-column path, forced through its switch
-    (DESIGN.md §3b): middle pass with the W_L table in LDS / with every output
-    of the last stage computed, F1 storing z from wave 0 / the one-wave F1:
-    float32, float64 and int16 batches == the oracle, bit for bit."""
+    """The live-column path with the serial F1 forced (serial-F1: nothing else
+    set -- these batches would otherwise take the time-split F1), and each
+    surviving path switch on top of it: the per-stream
+    decide kernel, the time-split F1 with convolution and with warm-up starts,
+    the exact path's F1 re-run instead of keep_z: float32, float64 and int16
+    batches == the oracle, bit for bit."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -561,3 +561,32 @@ sys.exit(1 if bad else 0)
     run_env.update(env)
     r = subprocess.run([sys.executable, str(script)], env=run_env, capture_output=True, text=True, timeout=250)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_fsk_live_generic_middle_pass():
+    """The live-column layout at a row length without a specialised kernel:
+    n = 1600 at sps 10 is a 40 x 40 grid, 40 = 8 x 5 with run-time radices, so
+    the middle pass is the generic four-wave k_fft_mid_live (96000's n1 = 300 =
+    20 x 15 takes the three-wave specialised one).  B = 33: one full group of
+    32 streams and a group of one.  float32 and int16 == the oracle, bit for
+    bit, with the call's own F1 (time-split at this batch size), with the serial
+    F1 (z kept through F2), and with every stream through the exact path
+    (mode 2: E2a / E2b / E3 on the same small live plan)."""
+    import _fsk
+    import synth
+    from oracle import oracle
+    B, N, baud, m, s = 33, 1600, 9600, 12000.0, 24000.0
+    x0 = synth.fsk_batch(B, N, baud, m, s, seed=34, distinct=5, noise=0.3)
+    pl = _fsk.FskPlan(N, baud, m, s, max_streams=B)
+    assert pl.live_columns
+    for x in (x0.astype(np.float32), np.round(np.clip(x0, -1, 1) * 32767).astype(np.int16)):
+        want = [oracle.fsk_demodulate(r, baud, m, s) for r in x]
+        assert len(want[0]) > 0
+        pl.set_exact_mode(1)
+        pl.set_layout("auto")
+        assert pl.demod_host(x)[0] == want
+        pl.set_layout("serial")
+        assert pl.demod_host(x)[0] == want
+        pl.set_exact_mode(2)
+        assert pl.demod_host(x)[0] == want
+        assert pl.exact_streams() == B
