@@ -307,3 +307,29 @@ def test_oracle_matches_reference_fsk_edges(case):
         warnings.simplefilter("ignore")
         got = ec.outcome(lambda: ec.demod(oracle, case, x, raw_int16=True))
     assert got == expected(case), (case["id"], case["params"])
+
+
+def _psk_edge_cases():
+    import psk_edge_cases as ec
+    return ec.load()[0]["cases"]
+
+
+@pytest.mark.parametrize("case", _psk_edge_cases(), ids=lambda c: c["id"])
+def test_oracle_matches_reference_psk_edges(case):
+    """The oracle against the reference's own qpsk_demodulate / bpsk_demodulate
+    at the edges of their parameter space (tests/golden/make_psk_edge_golden.py):
+    31.25 .. 110 Bd band-passes, designs whose band-pass output grows to
+    1e248 or overflows to inf / NaN (the bytes are decided from those),
+    low-passes with b[0] < 2^-50, clamped band edges, a carrier on fs / 4,
+    2 and 3 samples per symbol, fractional rates, and the parameters the
+    reference raises on (the same exception type and text).  Each input is
+    regenerated from its seed and must have the recorded SHA-256; int16
+    captures go in raw, as the reference got them."""
+    import warnings
+
+    import psk_edge_cases as ec
+    x = ec.case_input(case, ec.load()[1])
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        got = ec.outcome(lambda: ec.demod(oracle, case, x, raw_int16=True))
+    assert got == ec.expected(case), (case["id"], case["params"])
