@@ -85,6 +85,11 @@ EXPORTS = [
     "amr_dsss_plan_bytes_estimate", "amr_dsss_acquire_bytes_estimate", "amr_dsss_demod_host", "amr_dsss_demod_device",
     "amr_dsss_acquire_host", "amr_dsss_acquire_device", "amr_dsss_symbols_at_host", "amr_dsss_slice_host",
     "amr_dsss_soft_host", "amr_dsss_modulate_host",
+    "amr_msk_plan_create", "amr_msk_plan_destroy", "amr_msk_plan_synchronize", "amr_msk_plan_enable_timing",
+    "amr_msk_plan_timings", "amr_msk_plan_out_capacity", "amr_msk_plan_scratch_bytes",
+    "amr_msk_plan_bytes_estimate", "amr_msk_acquire_bytes_estimate", "amr_msk_demod_host", "amr_msk_demod_device",
+    "amr_msk_acquire_host", "amr_msk_acquire_device", "amr_msk_symbols_at_host", "amr_msk_offset_host",
+    "amr_msk_slice_host", "amr_msk_soft_host", "amr_msk_modulate_host",
 ]
 TO_NAMES = ["dft", "slice", "sync_pack", "launch"]
 TO_SLOTS = TO_NAMES + ["acquire"]                  # AMR_TO_*: "acquire" is run by an acquiring call only
@@ -501,6 +506,24 @@ def lib():
             "amr_dsss_slice_host": (I32, [P, I64, I64, P]),
             "amr_dsss_soft_host": (I32, [P, I64, I64, P]),
             "amr_dsss_modulate_host": (I32, [I64, I32, I64, P, P, P, I64, P, I64, P, I64, I64, P, I64]),
+            "amr_msk_plan_create": (I32, [P, I32, I64, I64, I64, P, P, P, P, I64]),
+            "amr_msk_plan_destroy": (I32, [P]),
+            "amr_msk_plan_synchronize": (I32, [P]),
+            "amr_msk_plan_enable_timing": (I32, [P, I32]),
+            "amr_msk_plan_timings": (I32, [P, P, I32]),
+            "amr_msk_plan_out_capacity": (I64, [P]),
+            "amr_msk_plan_scratch_bytes": (I64, [P]),
+            "amr_msk_plan_bytes_estimate": (I64, [I64, I64, I64]),
+            "amr_msk_acquire_bytes_estimate": (I64, [I64, I64, I64]),
+            "amr_msk_demod_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, I32]),
+            "amr_msk_demod_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, I32]),
+            "amr_msk_acquire_host": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_msk_acquire_device": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_msk_symbols_at_host": (I32, [P, P, I32, I64, I64, P, P]),
+            "amr_msk_offset_host": (I32, [I64, P, P, I64, P, P]),
+            "amr_msk_slice_host": (I32, [P, I64, I64, I64, P]),
+            "amr_msk_soft_host": (I32, [P, I64, I64, I64, P]),
+            "amr_msk_modulate_host": (I32, [I64, I64, P, P, I64, P, I64, P, I64, I64, P, I64]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1016,7 +1039,7 @@ def _rows(x: np.ndarray):
 
 
 class _SymPlan:
-    """What the symbol modems' plans (OfdmPlan, DsssPlan) share, over the amr_<_abi>_* entries: the handle's
+    """What the symbol modems' plans (OfdmPlan, DsssPlan, MskPlan) share, over the amr_<_abi>_* entries: the handle's
     lifetime, the batching of a call into max_streams streams at a time, the host demodulation and stage
     loops, and the plan accessors.  A subclass sets _abi and _slots and calls _create from its __init__."""
     _abi = ""
@@ -1354,6 +1377,143 @@ def dsss_soft(Y: np.ndarray) -> np.ndarray:
     B, S = Y.shape
     soft = np.zeros((B, max(0, S - 1)), np.int8)
     check(lib().amr_dsss_soft_host(ptr(Y), B, S, ptr(soft)))
+    return soft
+
+
+# ---------------------------------------------------------------------------
+# minshift: the MSK modem (tests/minshift_cases.py)
+def msk_geometry(baud, carrier, samp_rate=96000):
+    """(L, h, cyc4) of DESIGN.md §3m, or ValueError when the geometry is not valid (host
+    arithmetic, before any device work): L samples per bit, h = L // 2, cyc4 quarter-cycles
+    of carrier per bit."""
+    L = int(samp_rate / baud)
+    if L < 4:
+        raise ValueError("minshift: fewer than four samples per bit")
+    if L > 1 << 24:
+        raise ValueError(f"minshift: {L} samples per bit, more than 2^24")
+    cyc4 = int(np.floor(4 * float(carrier) * L / float(samp_rate) + 0.5))
+    if cyc4 < 2:
+        raise ValueError("minshift: less than half a carrier cycle per bit")
+    if cyc4 + 1 >= 2 * L:
+        raise ValueError(f"minshift: {cyc4} quarter-cycles in a bit of {L} samples, the upper tone at or above "
+                         "half the sample rate")
+    return L, L // 2, cyc4
+
+
+def design_msk(baud, carrier, samp_rate=96000):
+    """The geometry and the tables (float64): Sn [4 L] = sin((2 pi) * (p / (4 L)));
+    U [L][2] = (cos th, -sin th), th = (2 pi) * (((cyc4 * i) % (4 L)) / (4 L));
+    E0, E1 [2 L][2] = (cos th, -sin th), th = (2 pi) * ((((cyc4 -/+ 1) * r) % (2 L)) / (2 L));
+    R [L][2] = (cos, +sin)((2 pi) * (d / L)).  What the plan and the modulator take, and what
+    tests/minshift_cases.py correlates against."""
+    L, h, cyc4 = msk_geometry(baud, carrier, samp_rate)
+
+    def pair(th, sign):
+        return np.ascontiguousarray(np.stack([np.cos(th), sign * np.sin(th)], axis=-1), np.float64)
+    Sn = np.ascontiguousarray(np.sin((2 * np.pi) * (np.arange(4 * L, dtype=np.int64) / (4 * L))), np.float64)
+    i = np.arange(L, dtype=np.int64)
+    U = pair((2 * np.pi) * (((cyc4 * i) % (4 * L)) / (4 * L)), -1.0)
+    r = np.arange(2 * L, dtype=np.int64)
+    E0 = pair((2 * np.pi) * ((((cyc4 - 1) * r) % (2 * L)) / (2 * L)), -1.0)
+    E1 = pair((2 * np.pi) * ((((cyc4 + 1) * r) % (2 * L)) / (2 * L)), -1.0)
+    R = pair((2 * np.pi) * (i / L), 1.0)
+    return L, h, cyc4, Sn, U, E0, E1, R
+
+
+class MskPlan(_SymPlan):
+    """A device plan of the minshift demodulator: the tables in HBM + W and the bit words for max_streams streams."""
+    _abi = "msk"
+    _slots = TD_SLOTS
+
+    def __init__(self, n: int, baud, carrier, samp_rate=96000, max_streams=64, device=None):
+        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
+        self.L, self.h, self.cyc4, _, U, E0, E1, R = design_msk(baud, carrier, samp_rate)
+        self.S = max(0, (self.n + self.h) // self.L - 1)
+        self._create(device, max_streams, self.n, self.L, self.cyc4, ptr(U), ptr(E0), ptr(E1), ptr(R))
+
+    def demod_host(self, x: np.ndarray, soft=False, acquire=True):
+        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync,
+        list[int8 array] or None, offsets int64 [B]); acquire: each stream from its own acquired offset."""
+        return self._demod(x, "demod_host", soft, lambda sv, of: (*sv, ptr(of), 1 if acquire else 0))
+
+    def acquire(self, x: np.ndarray):
+        """The bit-timing stage alone (amr_msk_acquire_host): (offset int64 [B], q complex128 [B])."""
+        B = x.shape[0]
+        off, q = self._stage(x, "acquire_host", [np.empty(B, np.int64), np.empty((B, 2))])
+        return off, q.view(np.complex128)[..., 0]
+
+    def symbols_at(self, x: np.ndarray, offsets=None) -> np.ndarray:
+        """The window correlator alone at given per-stream offsets, default zeros (amr_msk_symbols_at_host):
+        W [B][Sw] complex128."""
+        offsets = np.zeros(x.shape[0], np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64)
+        W, = self._stage(x, "symbols_at_host", [np.zeros((x.shape[0], self.S, 2))], offsets)
+        return W.view(np.complex128)[..., 0]
+
+
+def get_msk_plan(n: int, baud, carrier, shape, samp_rate, batch: int, acquire=False) -> MskPlan:
+    """The shared plan cache, keyed by the call's parameters (and device); `shape` is unused (the symbol
+    modems' getters share one signature).  acquire: the plan is about to acquire; the first time, the cache
+    makes room for its acquisition buffers."""
+    dev = default_device()
+    L, h, cyc4 = msk_geometry(baud, carrier, samp_rate)                 # ValueError before any plan is evicted
+    key = ("msk", int(n), float(baud), float(carrier), float(samp_rate), dev)
+    need = stream_bucket(batch, PSK_MAX_CHUNK)
+
+    def estimate(m):
+        return max(0, int(lib().amr_msk_plan_bytes_estimate(int(n), L, m)))
+    pl = plan_cache.get(key, need, lambda m: MskPlan(n, baud, carrier, samp_rate, max_streams=m, device=dev), estimate)
+    if acquire:
+        _plan_acquires(pl, key, lambda: lib().amr_msk_acquire_bytes_estimate(int(n), L, pl.max_streams))
+    return pl
+
+
+def msk_tx_samples(n_bytes: int, baud, carrier, samp_rate=96000) -> int:
+    """len() of minshift_modulate's output for an n_bytes payload: (82 + 8 n) * L."""
+    return (82 + 8 * int(n_bytes)) * msk_geometry(baud, carrier, samp_rate)[0]
+
+
+def msk_modulate(datas, baud, carrier, samp_rate=96000, n_out=None, pcm=False):
+    """Batched minshift modulator on the GPU (amr_msk_modulate_host): [B][n_out]
+    float32, cut / zero-padded to n_out (default: the longest natural length);
+    pcm=True also returns wav_from_array's int16."""
+    L, h, cyc4, Sn, *_ = design_msk(baud, carrier, samp_rate)            # the geometry's ValueError
+    require_gpu()
+    if n_out is None:
+        n_out = max(((82 + 8 * len(d)) * L for d in datas), default=0)
+    check(lib().amr_set_device(default_device()))
+    rc, res = _modulate_call(datas, n_out, pcm, lambda *a: lib().amr_msk_modulate_host(L, cyc4, ptr(Sn), *a))
+    check(rc)
+    return res
+
+
+def msk_offset(c, baud, carrier, samp_rate=96000):
+    """The score and maximum stage alone on the GPU (k_msk_acq_max) on given line sums c [B][4] =
+    (c0.re, c0.im, c1.re, c1.im), one segment per stream: (offset int64 [B], q complex128 [B])."""
+    L, *_, R = design_msk(baud, carrier, samp_rate)
+    require_gpu()
+    c = np.ascontiguousarray(c, np.float64).reshape(-1, 4)
+    off, q = np.zeros(c.shape[0], np.int64), np.zeros((c.shape[0], 2))
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_msk_offset_host(L, ptr(R), ptr(c), c.shape[0], ptr(off), ptr(q)))
+    return off, q.view(np.complex128)[..., 0]
+
+
+def msk_slice(W: np.ndarray, cyc4: int) -> np.ndarray:
+    """The slicer stage alone on the GPU (k_msk_slice): W [B][Sw] complex128 -> the decided bits [B][Sw - 1] as uint8."""
+    require_gpu()
+    W = np.ascontiguousarray(W, np.complex128)
+    B, S = W.shape
+    return _slice_bits(B, max(0, S - 1), lambda w: lib().amr_msk_slice_host(ptr(W), B, S, int(cyc4), w))
+
+
+def msk_soft(W: np.ndarray, cyc4: int) -> np.ndarray:
+    """The soft stage alone on the GPU (k_msk_slice then k_msk_soft): W [B][Sw]
+    complex128 -> int8 [B][Sw - 1], one value per decided bit from bit 0."""
+    require_gpu()
+    W = np.ascontiguousarray(W, np.complex128)
+    B, S = W.shape
+    soft = np.zeros((B, max(0, S - 1)), np.int8)
+    check(lib().amr_msk_soft_host(ptr(W), B, S, int(cyc4), ptr(soft)))
     return soft
 
 

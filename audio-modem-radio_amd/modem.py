@@ -31,6 +31,12 @@ DBPSK modem beside the dsss_modulate alias the reference keeps (a BPSK call):
   acquire the code phase of a capture that starts anywhere by default, and
   spread_acquire (+ _batch), the acquisition alone.
 
+minshift (no reference counterpart): a real MSK modem beside
+the msk_modulate alias the reference keeps (an FSK call, modulation index 1):
+  minshift_modulate, minshift_demodulate (+ _batch, _soft, _soft_batch), which
+  recover the bit timing of a capture that starts anywhere by default, and
+  minshift_acquire (+ _batch), the bit timing alone.
+
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
@@ -239,11 +245,13 @@ def _spread_demod(plan, x2d, soft, acquire):
     return outs, softs
 
 
-# what differs between the two symbol modems (ofdm here, spread below) on the way to a plan's host
-# entries: the geometry check, the plan cache's getter and the plan's demodulation as (outs, softs).
-# `shape` in the functions below is ofdm's num_subcarriers / spread's code.
+# what differs between the symbol modems (ofdm here, spread and minshift below) on the way to a plan's
+# host entries: the geometry check, the plan cache's getter and the plan's demodulation as (outs, softs).
+# `shape` in the functions below is ofdm's num_subcarriers / spread's code / None for minshift.
 _SYM = {"ofdm": (_amr.ofdm_geometry, _amr.get_ofdm_plan, _ofdm_demod),
-        "spread": (_amr.dsss_geometry, _amr.get_dsss_plan, _spread_demod)}
+        "spread": (_amr.dsss_geometry, _amr.get_dsss_plan, _spread_demod),
+        "minshift": (lambda baud, carrier, shape, samp_rate: _amr.msk_geometry(baud, carrier, samp_rate),
+                     _amr.get_msk_plan, _spread_demod)}
 
 
 def _sym_row(name: str, samples) -> np.ndarray:
@@ -356,6 +364,49 @@ def spread_acquire_batch(samples, baud, carrier, code=None, samp_rate=96000) -> 
 def spread_acquire(samples, baud, carrier, code=None, samp_rate=96000) -> int:
     """spread_acquire_batch of one stream."""
     return int(spread_acquire_batch(_sym_row("spread_acquire", samples), baud, carrier, code, samp_rate)[0])
+
+
+# ---------------------------------------------------------------------------
+# minshift: MSK (DESIGN.md §3m), continuous phase and constant envelope, the two
+# tones half the bit rate apart.  One FP64 correlation per bit boundary, decided
+# differentially.  A capture may start anywhere: the bit timing (the default) is
+# read from the two spectral lines of the squared signal, with no search.
+# Samples as ofdm reads them.
+def minshift_demodulate(samples, baud, carrier, samp_rate=96000, acquire=True) -> bytes:
+    """MSK demodulation of one stream, on the GPU.  acquire=False: the capture starts on a
+    bit boundary (offset 0); the default finds the bit timing first (minshift_acquire)."""
+    x = _sym_row("minshift_demodulate", samples)
+    return _sym_batch("minshift", x, baud, carrier, None, samp_rate, acquire=acquire)[0]
+
+
+def minshift_demodulate_batch(samples, baud, carrier, samp_rate=96000, acquire=True) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == minshift_demodulate(row))."""
+    return _sym_batch("minshift", samples, baud, carrier, None, samp_rate, acquire=acquire)
+
+
+def minshift_demodulate_soft(samples, baud, carrier, samp_rate=96000, acquire=True):
+    """minshift_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _sym_row("minshift_demodulate_soft", samples)
+    outs, softs = _sym_batch("minshift", x, baud, carrier, None, samp_rate, soft=True, acquire=acquire)
+    return outs[0], softs[0]
+
+
+def minshift_demodulate_soft_batch(samples, baud, carrier, samp_rate=96000, acquire=True):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _sym_batch("minshift", samples, baud, carrier, None, samp_rate, soft=True, acquire=acquire)
+
+
+def minshift_acquire_batch(samples, baud, carrier, samp_rate=96000) -> np.ndarray:
+    """[B, N] equal-length streams -> int64 [B]: the sample offset in [0, L - 1] at which each
+    stream's bits begin, from the phase difference of the squared signal's two
+    spectral lines.  One offset per capture, on the sender's sample clock; a bit boundary
+    only: which bit is which is the sync word's business."""
+    return _sym_acquire("minshift", samples, baud, carrier, None, samp_rate)
+
+
+def minshift_acquire(samples, baud, carrier, samp_rate=96000) -> int:
+    """minshift_acquire_batch of one stream."""
+    return int(minshift_acquire_batch(_sym_row("minshift_acquire", samples), baud, carrier, samp_rate)[0])
 
 
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
@@ -543,6 +594,13 @@ def spread_modulate(data_bytes: bytes, baud, carrier, code=None, samp_rate=96000
     return _amr.dsss_modulate([bytes(data_bytes)], baud, carrier, code, samp_rate)[0]
 
 
+def minshift_modulate(data_bytes: bytes, baud, carrier, samp_rate=96000) -> np.ndarray:
+    """MSK: [0] + [1,0]*40 + the payload's bits + [0], a 1 as cyc4 + 1 and a 0
+    as cyc4 - 1 quarter-cycles of phase over the bit, the phase continuous and the envelope
+    constant; the tones are half the bit rate apart.  (82 + 8 len) * L samples."""
+    return _amr.msk_modulate([bytes(data_bytes)], baud, carrier, samp_rate)[0]
+
+
 def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False,
                    num_subcarriers=None, code=None):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
@@ -552,7 +610,9 @@ def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=9600
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
     pass baud=122.5 for the reference's default), or 'ofdm' (f0 = carrier,
     num_subcarriers required), or 'spread' (f0 = carrier, baud = the chip rate,
-    code: the chips, default _amr.DSSS_CODE)."""
+    code: the chips, default _amr.DSSS_CODE), or 'minshift' (f0 = carrier)."""
+    if kind == "minshift":
+        return _amr.msk_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, samp_rate, n_out, pcm)
     if kind == "spread":
         return _amr.dsss_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, code, samp_rate,
                                   n_out, pcm)

@@ -983,6 +983,100 @@ int amr_dsss_modulate_host(int64_t spc, int C, int64_t cyc, const double *cs, co
                            int64_t data_stride, const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride,
                            int64_t n_out, int16_t *pcm, int64_t pcm_stride);
 
+/* ---- minshift: an MSK modem with bit-timing recovery (no reference
+ * counterpart: the reference's msk_modulate calls FSK with tone spacing baud
+ * and it has no msk_demodulate; DESIGN.md §3m, tests/minshift_cases.py) --------
+ * Geometry for (L, cyc4): L samples per bit, h = L / 2, cyc4 quarter-cycles of
+ * carrier per bit; a 1 bit advances the phase by cyc4 + 1 quarter-cycles, a 0
+ * bit by cyc4 - 1.  Valid iff L >= 4, cyc4 >= 2, cyc4 + 1 < 2 L and L <= 2^24;
+ * anything else is AMR_E_INVALID before any device work.
+ * Tables (the caller's, float64): Sn [4 L] = sin((2 pi) * (p / (4 L)));
+ * U [L][2] = (cos th, -sin th), th = (2 pi) * (((cyc4 * i) % (4 L)) / (4 L));
+ * E0, E1 [2 L][2] = (cos th, -sin th), th = (2 pi) * ((((cyc4 -/+ 1) * r) %
+ * (2 L)) / (2 L)); R [L][2] = (cos, +sin)((2 pi) * (d / L)).
+ * Receiver at offset o in [0, L-1] (0 when not acquired): x' = shift(x, o) as
+ * for spread; Sw = max(0, (n + h) / L - 1) windows,
+ *   W[k] = sum over i < L of x'[(k+1) L - h + i] * U[i]
+ * in four interleaved partial sums p[i & 3], each sequential in i from 0.0,
+ * every product rounded before it is added (no fma), combined as (p0 + p1) +
+ * (p2 + p3) per component; D[k] = (W[k+1] * conj(W[k])) * (-i)^(cyc4 mod 4)
+ * (numpy's multiply, as the PSK slicers; the quarter-turns a swap and
+ * negation); the bit is 1 iff D.imag > 0 (NaN and zeros give 0): Sw - 1 bits
+ * per stream, sync search and byte pack as for the PSK plans.  Sw < 2: no
+ * bytes, sync index -1.
+ * Soft values: one int8 per product, the hard bit's sign, the magnitude of
+ * amr_psk_soft_host's BPSK rule with D.imag in the role of the real part,
+ * aligned to the bytes as amr_psk_demod_soft_*.
+ * Bit timing, per stream of n samples, t = 0, 1:
+ *   c_t   = sum over m < n of (x[m] * x[m]) * E_t[m % (2 L)], the square rounded
+ *           first, then each component product.  Order: segments of 4096
+ *           samples; in a segment partial j of 64 adds m = 4096 seg + 64 a + j
+ *           sequentially in a from 0.0; the partials by the tree j with j + 32,
+ *           then 16, 8, 4, 2, 1; the segment sums in order from 0.0
+ *   q     = c1 * conj(c0) = (c1r c0r + c1i c0i, c1i c0r - c1r c0i)
+ *   P[d]  = q.re * R[d].re - q.im * R[d].im
+ *   o     = best after: best = 0; for d = 1 .. L - 1: if (P[d] > P[best]) best = d
+ * The bit-timing buffers are allocated on the plan's first acquiring call
+ * (then part of amr_msk_plan_scratch_bytes); amr_msk_acquire_bytes_estimate is
+ * their size by host arithmetic (< 0: bad shape).  The timing slots are
+ * AMR_TD_*: AMR_TD_DESPREAD is k_msk_corr, AMR_TD_ACQUIRE k_msk_lines and
+ * k_msk_acq_max. */
+typedef struct amr_msk_plan amr_msk_plan;
+int amr_msk_plan_create(amr_msk_plan **plan, int device, int64_t n_samples, int64_t L, int64_t cyc4, const double *U,
+                        const double *E0, const double *E1, const double *R, int64_t max_streams);
+int amr_msk_plan_destroy(amr_msk_plan *plan);
+int amr_msk_plan_synchronize(amr_msk_plan *plan);
+int amr_msk_plan_enable_timing(amr_msk_plan *plan, int on);
+/* milliseconds of each AMR_TD_* slot in the last call (-1 = not run) */
+int amr_msk_plan_timings(amr_msk_plan *plan, float *ms, int count);
+/* bytes an output row needs ((Sw - 1) / 8 + 1), or -1 */
+int64_t amr_msk_plan_out_capacity(const amr_msk_plan *plan);
+/* device bytes the plan holds now, and (host arithmetic) what a plan of this
+ * shape holds once its host entries have staged a full batch; < 0: bad shape */
+int64_t amr_msk_plan_scratch_bytes(const amr_msk_plan *plan);
+int64_t amr_msk_plan_bytes_estimate(int64_t n_samples, int64_t L, int64_t max_streams);
+int64_t amr_msk_acquire_bytes_estimate(int64_t n_samples, int64_t L, int64_t max_streams);
+/* the amr_dsss_demod_* shapes and argument contract: soft and offset may be
+ * NULL; acquire != 0: every stream is read from its acquired offset, else from
+ * 0 (offset then receives zeros).  Bit timing, correlator, slicer, sync / pack
+ * and soft values are queued on the plan's stream with no host round trip in
+ * between. */
+int amr_msk_demod_host(amr_msk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                       uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx, int8_t *soft,
+                       int64_t soft_stride, int64_t *offset, int acquire);
+int amr_msk_demod_device(amr_msk_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                         uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                         int8_t *d_soft, int64_t soft_stride, int64_t *d_offset, int acquire);
+/* the bit-timing stage alone: offset [n_streams] and q [n_streams][2]; q may
+ * be NULL.  _device: device pointers, queued on the plan's stream. */
+int amr_msk_acquire_host(amr_msk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                         int64_t *offset, double *q);
+int amr_msk_acquire_device(amr_msk_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                           int64_t *d_offset, double *d_q);
+/* the correlator alone at given offsets: W [n_streams][Sw][2] of shift(x[b],
+ * offset[b]); an offset outside [0, L - 1] is AMR_E_INVALID before any device work */
+int amr_msk_symbols_at_host(amr_msk_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                            const int64_t *offset, double *W);
+/* the score and maximum stage alone on given line sums c [n_streams][4] =
+ * (c0.re, c0.im, c1.re, c1.im), taken as one segment (0.0 + c); R [L][2];
+ * offset [n_streams], q [n_streams][2] or NULL */
+int amr_msk_offset_host(int64_t L, const double *R, const double *c, int64_t n_streams, int64_t *offset, double *q);
+/* the slicer and soft stages alone on given W [n_streams][n_win][2]: words
+ * [n_streams][max(1, ceil((n_win - 1) / 32))] (MSB first), soft
+ * [n_streams][n_win - 1] (every bit from 0); cyc4 >= 0, only cyc4 mod 4 counts */
+int amr_msk_slice_host(const double *W, int64_t n_streams, int64_t n_win, int64_t cyc4, uint32_t *words);
+int amr_msk_soft_host(const double *W, int64_t n_streams, int64_t n_win, int64_t cyc4, int8_t *soft);
+/* minshift_modulate: the bits [0] + [1,0]*40 + payload (MSB first) + [0]; the
+ * integer phase p in units of 1 / (4 L) cycle, p_0 = 0, p_{k+1} = (p_k + L *
+ * inc_k) % (4 L), inc_k = cyc4 + 1 for a 1 and cyc4 - 1 for a 0; sample i of bit
+ * k is float32(Sn[(p_k + i * inc_k) % (4 L)]): the sine is the caller's table,
+ * so the output is the restatement's bit for bit.  A frame of an n_bytes
+ * payload is (82 + 8 n_bytes) * L samples; out / pcm / n_out as
+ * amr_modulate_host. */
+int amr_msk_modulate_host(int64_t L, int64_t cyc4, const double *Sn, const uint8_t *data, int64_t data_stride,
+                          const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride, int64_t n_out,
+                          int16_t *pcm, int64_t pcm_stride);
+
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
  * the deviate hashed from (seed, s, i): distinct noisy batches over the same
