@@ -90,6 +90,12 @@ EXPORTS = [
     "amr_msk_plan_bytes_estimate", "amr_msk_acquire_bytes_estimate", "amr_msk_demod_host", "amr_msk_demod_device",
     "amr_msk_acquire_host", "amr_msk_acquire_device", "amr_msk_symbols_at_host", "amr_msk_offset_host",
     "amr_msk_slice_host", "amr_msk_soft_host", "amr_msk_modulate_host",
+    "amr_tone8_chunk", "amr_tone8_plan_create", "amr_tone8_plan_destroy", "amr_tone8_plan_synchronize",
+    "amr_tone8_plan_enable_timing", "amr_tone8_plan_timings", "amr_tone8_plan_out_capacity",
+    "amr_tone8_plan_scratch_bytes", "amr_tone8_plan_bytes_estimate", "amr_tone8_acquire_bytes_estimate",
+    "amr_tone8_demod_host", "amr_tone8_demod_device", "amr_tone8_acquire_host", "amr_tone8_acquire_device",
+    "amr_tone8_symbols_at_host", "amr_tone8_peak_host", "amr_tone8_slice_host", "amr_tone8_soft_host",
+    "amr_tone8_modulate_host",
 ]
 TO_NAMES = ["dft", "slice", "sync_pack", "launch"]
 TO_SLOTS = TO_NAMES + ["acquire"]                  # AMR_TO_*: "acquire" is run by an acquiring call only
@@ -524,6 +530,25 @@ def lib():
             "amr_msk_slice_host": (I32, [P, I64, I64, I64, P]),
             "amr_msk_soft_host": (I32, [P, I64, I64, I64, P]),
             "amr_msk_modulate_host": (I32, [I64, I64, P, P, I64, P, I64, P, I64, I64, P, I64]),
+            "amr_tone8_chunk": (I64, [I64]),
+            "amr_tone8_plan_create": (I32, [P, I32, I64, I64, I64, I64, P, I64]),
+            "amr_tone8_plan_destroy": (I32, [P]),
+            "amr_tone8_plan_synchronize": (I32, [P]),
+            "amr_tone8_plan_enable_timing": (I32, [P, I32]),
+            "amr_tone8_plan_timings": (I32, [P, P, I32]),
+            "amr_tone8_plan_out_capacity": (I64, [P]),
+            "amr_tone8_plan_scratch_bytes": (I64, [P]),
+            "amr_tone8_plan_bytes_estimate": (I64, [I64, I64, I64, I64]),
+            "amr_tone8_acquire_bytes_estimate": (I64, [I64, I64, I64, I64]),
+            "amr_tone8_demod_host": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, P, I32]),
+            "amr_tone8_demod_device": (I32, [P, P, I32, I64, I64, P, I64, P, P, P, I64, P, P, I32]),
+            "amr_tone8_acquire_host": (I32, [P, P, I32, I64, I64, P, P, P]),
+            "amr_tone8_acquire_device": (I32, [P, P, I32, I64, I64, P, P, P]),
+            "amr_tone8_symbols_at_host": (I32, [P, P, I32, I64, I64, P, P, P]),
+            "amr_tone8_peak_host": (I32, [I64, I64, P, I64, I64, P, P, P]),
+            "amr_tone8_slice_host": (I32, [P, I64, I64, P]),
+            "amr_tone8_soft_host": (I32, [P, I64, I64, P]),
+            "amr_tone8_modulate_host": (I32, [I64, I64, P, P, I64, P, I64, P, I64, I64, P, I64]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1514,6 +1539,170 @@ def msk_soft(W: np.ndarray, cyc4: int) -> np.ndarray:
     B, S = W.shape
     soft = np.zeros((B, max(0, S - 1)), np.int8)
     check(lib().amr_msk_soft_host(ptr(W), B, S, int(cyc4), ptr(soft)))
+    return soft
+
+
+# ---------------------------------------------------------------------------
+# tone8: the 8-FSK modem with Costas sync (tests/tone8_cases.py)
+TONE8_COSTAS = (3, 1, 4, 0, 6, 5, 2)
+TONE8_SEARCH = 6                                   # the default search, half tone spacings either way
+TONE8_MAX_SEARCH = 16
+
+
+def tone8_geometry(baud, carrier, samp_rate=96000, search=TONE8_SEARCH):
+    """(L, T, c2, G) of DESIGN.md §3n, or ValueError when the geometry is not valid (host
+    arithmetic, before any device work): L samples per symbol, T = L // 8 per time slot, c2
+    half-cycles of carrier per symbol (tone m has c2 + 2 m), G = search half tone spacings
+    looked through either way."""
+    G = int(search)
+    if G != search or not 0 <= G <= TONE8_MAX_SEARCH:
+        raise ValueError(f"tone8: search {search!r} outside 0..{TONE8_MAX_SEARCH}")
+    L = int(samp_rate / baud)
+    if L < 8 or L % 8:
+        raise ValueError(f"tone8: {L} samples per symbol, not a positive multiple of 8")
+    if L > 1 << 24:
+        raise ValueError(f"tone8: {L} samples per symbol, more than 2^24")
+    c2 = int(np.floor(2 * float(carrier) * L / float(samp_rate) + 0.5))
+    if c2 - G < 2:
+        raise ValueError(f"tone8: {c2} half-cycles of carrier per symbol, the lowest searched line below one cycle")
+    if c2 + 14 + G >= L:
+        raise ValueError(f"tone8: {c2} half-cycles in a symbol of {L} samples, the highest searched line at or above "
+                         "half the sample rate")
+    return L, L // 8, c2, G
+
+
+def design_tone8(baud, carrier, samp_rate=96000, search=TONE8_SEARCH):
+    """The geometry and the tables (float64): Sn [2 L] = sin((2 pi) * (p / (2 L)));
+    E [2 L][2] = (cos th, -sin th), th = (2 pi) * (r / (2 L)).  What the plan and the modulator
+    take, and what tests/tone8_cases.py correlates against."""
+    L, T, c2, G = tone8_geometry(baud, carrier, samp_rate, search)
+    th = (2 * np.pi) * (np.arange(2 * L, dtype=np.int64) / (2 * L))
+    Sn = np.ascontiguousarray(np.sin(th), np.float64)
+    E = np.ascontiguousarray(np.stack([np.cos(th), -np.sin(th)], axis=-1), np.float64)
+    return L, T, c2, G, Sn, E
+
+
+def tone8_chunk(search=TONE8_SEARCH) -> int:
+    """Start slots one acquisition workgroup takes at this search (amr_tone8_chunk)."""
+    v = int(lib().amr_tone8_chunk(int(search)))
+    if v < 0:
+        check(v)                                   # the AMR_E_* of a search outside 0..16
+    return v
+
+
+class Tone8Plan(_SymPlan):
+    """A device plan of the tone8 demodulator: the table in HBM + Y and the bit words for max_streams streams."""
+    _abi = "tone8"
+    _slots = TD_SLOTS
+
+    def __init__(self, n: int, baud, carrier, samp_rate=96000, search=TONE8_SEARCH, max_streams=64, device=None):
+        self.n, self.baud, self.carrier, self.samp_rate = int(n), baud, carrier, samp_rate
+        self.L, self.T, self.c2, self.G, _, E = design_tone8(baud, carrier, samp_rate, search)
+        self.S = self.n // self.L
+        self._create(device, max_streams, self.n, self.L, self.c2, self.G, ptr(E))
+
+    def demod_host(self, x: np.ndarray, soft=False, acquire=True):
+        """x [B][N] float32 / float64 / int16 (PCM, read as int16 / 32768).  Returns (list[bytes], sync,
+        list[int8 array] or None, start int64 [B], shift int64 [B]); acquire: each stream at its own
+        acquired (start, shift), else at (0, 0)."""
+        shifts, at = np.zeros(x.shape[0], np.int64), [0]
+
+        def tail(sv, of):
+            sh = shifts[at[0]:at[0] + of.size]               # the batches come in order
+            at[0] += of.size
+            return (*sv, ptr(of), ptr(sh), 1 if acquire else 0)
+        return (*self._demod(x, "demod_host", soft, tail), shifts)
+
+    def acquire(self, x: np.ndarray):
+        """The acquisition stage alone (amr_tone8_acquire_host): (start int64 [B], shift int64 [B],
+        score float64 [B])."""
+        B = x.shape[0]
+        return tuple(self._stage(x, "acquire_host", [np.empty(B, np.int64), np.empty(B, np.int64), np.empty(B)]))
+
+    def symbols_at(self, x: np.ndarray, offsets=None, shifts=None) -> np.ndarray:
+        """The DFT stage alone at given per-stream (offset, shift), default zeros (amr_tone8_symbols_at_host):
+        Y [B][S][8] complex128."""
+        B = x.shape[0]
+        offsets = np.zeros(B, np.int64) if offsets is None else np.ascontiguousarray(offsets, np.int64)
+        shifts = np.zeros(B, np.int64) if shifts is None else np.ascontiguousarray(shifts, np.int64)
+        Y = np.zeros((B, self.S, 8, 2))
+        for s0, xb, stride in self._batches(x):
+            nb = xb.shape[0]
+            of, sh = np.ascontiguousarray(offsets[s0:s0 + nb]), np.ascontiguousarray(shifts[s0:s0 + nb])
+            with self.lock:
+                check(self._fn("symbols_at_host")(self.handle, ptr(xb), DTYPES[xb.dtype], nb, stride, ptr(of), ptr(sh),
+                                                  ptr(Y[s0:s0 + nb])))
+        return Y.view(np.complex128)[..., 0]
+
+
+def get_tone8_plan(n: int, baud, carrier, shape, samp_rate, batch: int, acquire=False) -> Tone8Plan:
+    """The shared plan cache, keyed by the call's parameters, the search (`shape`, None: the default) among
+    them (and device).  acquire: the plan is about to acquire; the first time, the cache makes room for its
+    acquisition buffers."""
+    dev = default_device()
+    search = TONE8_SEARCH if shape is None else shape
+    L, T, c2, G = tone8_geometry(baud, carrier, samp_rate, search)      # ValueError before any plan is evicted
+    key = ("tone8", int(n), float(baud), float(carrier), G, float(samp_rate), dev)
+    need = stream_bucket(batch, PSK_MAX_CHUNK)
+
+    def estimate(m):
+        return max(0, int(lib().amr_tone8_plan_bytes_estimate(int(n), L, G, m)))
+    pl = plan_cache.get(key, need, lambda m: Tone8Plan(n, baud, carrier, samp_rate, G, max_streams=m, device=dev),
+                        estimate)
+    if acquire:
+        _plan_acquires(pl, key, lambda: lib().amr_tone8_acquire_bytes_estimate(int(n), L, G, pl.max_streams))
+    return pl
+
+
+def tone8_tx_samples(n_bytes: int, baud, carrier, samp_rate=96000) -> int:
+    """len() of tone8_modulate's output for an n_bytes payload: (7 + ceil(8 n / 3)) * L."""
+    return (7 + -(-8 * int(n_bytes) // 3)) * tone8_geometry(baud, carrier, samp_rate, 0)[0]
+
+
+def tone8_modulate(datas, baud, carrier, samp_rate=96000, n_out=None, pcm=False):
+    """Batched tone8 modulator on the GPU (amr_tone8_modulate_host): [B][n_out]
+    float32, cut / zero-padded to n_out (default: the longest natural length);
+    pcm=True also returns wav_from_array's int16."""
+    L, T, c2, G, Sn, _ = design_tone8(baud, carrier, samp_rate, 0)       # the geometry's ValueError
+    require_gpu()
+    if n_out is None:
+        n_out = max(((7 + -(-8 * len(d) // 3)) * L for d in datas), default=0)
+    check(lib().amr_set_device(default_device()))
+    rc, res = _modulate_call(datas, n_out, pcm, lambda *a: lib().amr_tone8_modulate_host(L, c2, ptr(Sn), *a))
+    check(rc)
+    return res
+
+
+def tone8_peak(P, T: int, search: int):
+    """The score and maximum stage alone on the GPU (k_tone8_peak, k_tone8_acq_max) on given window
+    energies P [B][n_win][15 + 2 search]: (start int64 [B], shift int64 [B], score float64 [B])."""
+    P = np.ascontiguousarray(P, np.float64)
+    B, nw, NB = P.shape
+    if NB != 15 + 2 * int(search):
+        raise ValueError(f"tone8_peak: {NB} lines, not 15 + 2 * {search}")
+    require_gpu()
+    start, shift, score = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B)
+    check(lib().amr_set_device(default_device()))
+    check(lib().amr_tone8_peak_host(int(T), int(search), ptr(P), B, nw, ptr(start), ptr(shift), ptr(score)))
+    return start, shift, score
+
+
+def tone8_slice(Y: np.ndarray) -> np.ndarray:
+    """The slicer stage alone on the GPU (k_tone8_slice): Y [B][S][8] complex128 -> the decided bits [B][3 S] as uint8."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S, _ = Y.shape
+    return _slice_bits(B, 3 * S, lambda w: lib().amr_tone8_slice_host(ptr(Y), B, S, w))
+
+
+def tone8_soft(Y: np.ndarray) -> np.ndarray:
+    """The soft stage alone on the GPU (k_tone8_slice then k_tone8_soft): Y [B][S][8]
+    complex128 -> int8 [B][3 S], one value per decided bit from bit 0."""
+    require_gpu()
+    Y = np.ascontiguousarray(Y, np.complex128)
+    B, S, _ = Y.shape
+    soft = np.zeros((B, 3 * S), np.int8)
+    check(lib().amr_tone8_soft_host(ptr(Y), B, S, ptr(soft)))
     return soft
 
 

@@ -255,13 +255,15 @@ int symbols_round_trip(Plan* plan, const void* x, int dtype, int64_t B, int64_t 
 // *_slice_host / _soft_host: the slicer on given Y (the words to `words`, or null), with `soft` the soft kernel,
 // every bit from 0.  p: the modem's params with its own fields set; a symbol is sym_vals complex values and
 // sym_bits bits.  slice: hipError_t(Y, p, words), soft_k: hipError_t(Y, p, words, soft), device pointers.
+// ref_syms: the symbols that carry no bits of their own: 1 for a differential modem (the first is the
+// reference), 0 where every symbol carries bits (tone8).
 template <class Params, class Slice, class SoftK>
 int symbol_stages(const char* who, Params p, int64_t sym_vals, int64_t sym_bits, const double* Y, int64_t n_streams,
-                  int64_t n_sym, uint32_t* words, int8_t* soft, Slice&& slice, SoftK&& soft_k) {
+                  int64_t n_sym, uint32_t* words, int8_t* soft, Slice&& slice, SoftK&& soft_k, int64_t ref_syms = 1) {
   if (n_streams < 0 || n_sym < 0 || (n_streams && n_sym && (!Y || (!words && !soft))))
     return fail(AMR_E_INVALID, std::string(who) + ": bad argument");
   p.n_sym = n_sym;
-  p.n_bits = n_sym >= 2 ? sym_bits * (n_sym - 1) : 0;
+  p.n_bits = n_sym > ref_syms ? sym_bits * (n_sym - ref_syms) : 0;
   p.n_words = p.n_bits > 0 ? (p.n_bits + 31) / 32 : 1;
   if (n_streams == 0 || p.n_bits == 0) return AMR_OK;
   const auto bad = hip_fail_as(who);

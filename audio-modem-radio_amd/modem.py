@@ -37,6 +37,12 @@ the msk_modulate alias the reference keeps (an FSK call, modulation index 1):
   recover the bit timing of a capture that starts anywhere by default, and
   minshift_acquire (+ _batch), the bit timing alone.
 
+tone8 (no reference counterpart): a real 8-FSK modem with
+Costas sync beside the ft8_* aliases the reference keeps (two-tone FSK calls):
+  tone8_modulate, tone8_demodulate (+ _batch, _soft, _soft_batch), which find
+  where a capture's frame starts and how far its tones are off the receiver's
+  carrier by default, and tone8_acquire (+ _batch), that search alone.
+
 Transmit side (on the GPU: tx_kernels.hip):
   qpsk_modulate modem.py:138-186   bpsk_modulate modem.py:28-65
   fsk_modulate  modem.py:270-295   (+ aliases) and modulate_batch; the float32
@@ -409,6 +415,64 @@ def minshift_acquire(samples, baud, carrier, samp_rate=96000) -> int:
     return int(minshift_acquire_batch(_sym_row("minshift_acquire", samples), baud, carrier, samp_rate)[0])
 
 
+# ---------------------------------------------------------------------------
+# tone8: 8-FSK with Costas sync, continuous phase and constant
+# envelope, eight orthogonal tones one symbol rate apart, three bits per symbol,
+# nothing differential.  A capture may start anywhere and its sender may sit up
+# to `search` half tone spacings off the receiver's carrier: acquisition (the
+# default) finds both with one 2-D correlation of the 7x7 Costas block over the
+# capture's spectrogram.  Samples as ofdm reads them.
+def _tone8_demod(plan, x2d, soft, acquire):
+    outs, _, softs, _, _ = plan.demod_host(x2d, soft=soft, acquire=acquire)
+    return outs, softs
+
+
+_SYM["tone8"] = (lambda baud, carrier, shape, samp_rate: _amr.tone8_geometry(baud, carrier, samp_rate, shape),
+                 _amr.get_tone8_plan, _tone8_demod)
+
+
+def tone8_demodulate(samples, baud, carrier, samp_rate=96000, acquire=True, search=6) -> bytes:
+    """8-FSK demodulation of one stream, on the GPU.  acquire=False: the capture starts on a symbol
+    boundary and its tones sit on the receiver's (`search` is not used); the default finds both first
+    (tone8_acquire), which needs carrier / baud >= 1 + search / 4."""
+    x = _sym_row("tone8_demodulate", samples)
+    return _sym_batch("tone8", x, baud, carrier, search if acquire else 0, samp_rate, acquire=acquire)[0]
+
+
+def tone8_demodulate_batch(samples, baud, carrier, samp_rate=96000, acquire=True, search=6) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == tone8_demodulate(row))."""
+    return _sym_batch("tone8", samples, baud, carrier, search if acquire else 0, samp_rate, acquire=acquire)
+
+
+def tone8_demodulate_soft(samples, baud, carrier, samp_rate=96000, acquire=True, search=6):
+    """tone8_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes))."""
+    x = _sym_row("tone8_demodulate_soft", samples)
+    outs, softs = _sym_batch("tone8", x, baud, carrier, search if acquire else 0, samp_rate, soft=True, acquire=acquire)
+    return outs[0], softs[0]
+
+
+def tone8_demodulate_soft_batch(samples, baud, carrier, samp_rate=96000, acquire=True, search=6):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _sym_batch("tone8", samples, baud, carrier, search if acquire else 0, samp_rate, soft=True, acquire=acquire)
+
+
+def tone8_acquire_batch(samples, baud, carrier, samp_rate=96000, search=6):
+    """[B, N] equal-length streams -> (start int64 [B], shift int64 [B]): the sample at
+    which each stream's Costas block begins, on a grid of L // 8 samples, and how far the sender's tones
+    are from the receiver's in half tone spacings (baud / 2 Hz each), -search .. search.  One pair per
+    capture, on the sender's sample clock; neither is refined, and there is no confidence value."""
+    x2d, plan = _sym_plan("tone8", samples, baud, carrier, search, samp_rate, True)
+    if plan is None:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    return plan.acquire(x2d)[:2]
+
+
+def tone8_acquire(samples, baud, carrier, samp_rate=96000, search=6):
+    """tone8_acquire_batch of one stream: (start, shift)."""
+    start, shift = tone8_acquire_batch(_sym_row("tone8_acquire", samples), baud, carrier, samp_rate, search)
+    return int(start[0]), int(shift[0])
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):
@@ -601,6 +665,14 @@ def minshift_modulate(data_bytes: bytes, baud, carrier, samp_rate=96000) -> np.n
     return _amr.msk_modulate([bytes(data_bytes)], baud, carrier, samp_rate)[0]
 
 
+def tone8_modulate(data_bytes: bytes, baud, carrier, samp_rate=96000) -> np.ndarray:
+    """8-FSK with Costas sync: the Costas block 3, 1, 4, 0, 6, 5, 2, then the payload's
+    bits three per symbol (MSB first, zero-padded), tribit v on tone v ^ (v >> 1); tone m has c2 + 2 m
+    half-cycles per symbol, the phase continuous and the envelope constant.  (7 + ceil(8 len / 3)) * L
+    samples."""
+    return _amr.tone8_modulate([bytes(data_bytes)], baud, carrier, samp_rate)[0]
+
+
 def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=96000, n_out=None, pcm=False,
                    num_subcarriers=None, code=None):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
@@ -610,7 +682,9 @@ def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=9600
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
     pass baud=122.5 for the reference's default), or 'ofdm' (f0 = carrier,
     num_subcarriers required), or 'spread' (f0 = carrier, baud = the chip rate,
-    code: the chips, default _amr.DSSS_CODE), or 'minshift' (f0 = carrier)."""
+    code: the chips, default _amr.DSSS_CODE), or 'minshift' or 'tone8' (f0 = carrier)."""
+    if kind == "tone8":
+        return _amr.tone8_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, samp_rate, n_out, pcm)
     if kind == "minshift":
         return _amr.msk_modulate([bytes(d) for d in datas], baud, 3000.0 if f0 is None else f0, samp_rate, n_out, pcm)
     if kind == "spread":

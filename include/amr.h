@@ -1077,6 +1077,97 @@ int amr_msk_modulate_host(int64_t L, int64_t cyc4, const double *Sn, const uint8
                           const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride, int64_t n_out,
                           int16_t *pcm, int64_t pcm_stride);
 
+/* ---- tone8: an 8-FSK modem with Costas sync (no reference counterpart: the
+ * reference's ft8_modulate calls FSK with two tones at 50 Bd; DESIGN.md §3n,
+ * tests/tone8_cases.py) ------------------------------------------------------
+ * Geometry for (L, c2, search): L samples per symbol, T = L / 8 samples per
+ * time slot, c2 half-cycles of carrier per symbol; tone m (0..7) has c2 + 2 m.
+ * G = search half tone spacings are looked through either way: the lines f =
+ * c2 - G .. c2 + 14 + G, NB = 15 + 2 G of them.  Valid iff L % 8 == 0, L <=
+ * 2^24, 0 <= G <= 16, c2 - G >= 2 and c2 + 14 + G < L; anything else is
+ * AMR_E_INVALID before any device work.  E [2 L][2] = (cos th, -sin th), th =
+ * (2 pi) * (r / (2 L)), is the caller's table (numpy's libm).  A frame is the
+ * Costas block 3, 1, 4, 0, 6, 5, 2, then the payload's tribits (MSB first,
+ * zero-padded), tribit v on tone v ^ (v >> 1); nothing is differential.
+ * Acquisition, float64, no fma, every product rounded before it is added:
+ *   Z[j][f]  = sum_{i<T} x[j T + i] * E[(f (j T + i)) % (2 L)], sequential in i from 0.0, j < J = n / T
+ *   Wd[j][f] = ((Z[j] + Z[j+1]) + (Z[j+2] + Z[j+3])) + ((Z[j+4] + Z[j+5]) + (Z[j+6] + Z[j+7])), j < J - 7
+ *   P[j][f]  = re * re + im * im
+ *   S[j][g]  = sum over s = 0..6 in order from 0.0 of P[j + 8 s][c2 + g + 2 costas[s]], j < nj = J - 55, |g| <= G
+ *   (j*, g*) = best after: best = (0, -G); for j ascending, g ascending: if (S[j][g] > S[best]) best = (j, g)
+ *   start = j* T, shift = g*, score = S[j*][g*]; nj <= 0: start = 0, shift = 0, score = 0.0
+ * Demodulation reads stream b from o = start % L with every tone moved by
+ * shift half-cycles per symbol (samples past the capture 0.0):
+ *   Y[k][m]  = sum_{i<L} x[o + k L + i] * E[((c2 + g + 2 m) i) % (2 L)], k < S = n / L: four interleaved
+ *              partial sums p[i & 3], each sequential in i from 0.0, (p0 + p1) + (p2 + p3)
+ *   tone     = the first maximum of e_m = re * re + im * im from m = 0 (strictly greater; a NaN never wins)
+ *   bits     = the tone's tribit t ^ (t >> 1) ^ (t >> 2), MSB first: 3 S bits into the PSK sync search and pack
+ *   soft     = one int8 per bit: a1 / a0 the largest e_m among the four tones whose tribit has the bit set /
+ *              clear (a NaN loses), magnitude as amr_psk_demod_soft_* from |a1 - a0| over a1 + a0, the hard bit's sign
+ * The acquisition buffers are allocated on the plan's first acquiring call
+ * (then part of amr_tone8_plan_scratch_bytes); amr_tone8_acquire_bytes_estimate
+ * is their size by host arithmetic (< 0: bad shape).  The timing slots are
+ * AMR_TD_*: AMR_TD_DESPREAD is k_tone8_dft, AMR_TD_ACQUIRE k_tone8_acq and
+ * k_tone8_acq_max. */
+typedef struct amr_tone8_plan amr_tone8_plan;
+/* start slots one acquisition workgroup takes at this search (the kernel's chunk C), or < 0 */
+int64_t amr_tone8_chunk(int64_t search);
+int amr_tone8_plan_create(amr_tone8_plan **plan, int device, int64_t n_samples, int64_t L, int64_t c2, int64_t search,
+                          const double *E, int64_t max_streams);
+int amr_tone8_plan_destroy(amr_tone8_plan *plan);
+int amr_tone8_plan_synchronize(amr_tone8_plan *plan);
+int amr_tone8_plan_enable_timing(amr_tone8_plan *plan, int on);
+/* milliseconds of each AMR_TD_* slot in the last call (-1 = not run) */
+int amr_tone8_plan_timings(amr_tone8_plan *plan, float *ms, int count);
+/* bytes an output row needs (3 S / 8 + 1), or -1 */
+int64_t amr_tone8_plan_out_capacity(const amr_tone8_plan *plan);
+/* device bytes the plan holds now, and (host arithmetic) what a plan of this
+ * shape holds once its host entries have staged a full batch; < 0: bad shape */
+int64_t amr_tone8_plan_scratch_bytes(const amr_tone8_plan *plan);
+int64_t amr_tone8_plan_bytes_estimate(int64_t n_samples, int64_t L, int64_t search, int64_t max_streams);
+int64_t amr_tone8_acquire_bytes_estimate(int64_t n_samples, int64_t L, int64_t search, int64_t max_streams);
+/* the amr_msk_demod_* shapes and argument contract: soft, start and shift may
+ * be NULL; acquire != 0: every stream is read at its acquired (start, shift),
+ * else at (0, 0) (start and shift then receive zeros).  Acquisition, DFT,
+ * slicer, sync / pack and soft values are queued on the plan's stream with no
+ * host round trip in between. */
+int amr_tone8_demod_host(amr_tone8_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                         uint8_t *out, int64_t out_stride, int64_t *out_len, int64_t *sync_idx, int8_t *soft,
+                         int64_t soft_stride, int64_t *start, int64_t *shift, int acquire);
+int amr_tone8_demod_device(amr_tone8_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                           uint8_t *d_out, int64_t out_stride, int64_t *d_out_len, int64_t *d_sync_idx,
+                           int8_t *d_soft, int64_t soft_stride, int64_t *d_start, int64_t *d_shift, int acquire);
+/* the acquisition stage alone: start, shift [n_streams] and score [n_streams];
+ * score may be NULL.  _device: device pointers, queued on the plan's stream. */
+int amr_tone8_acquire_host(amr_tone8_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                           int64_t *start, int64_t *shift, double *score);
+int amr_tone8_acquire_device(amr_tone8_plan *plan, const void *d_x, int dtype, int64_t n_streams, int64_t x_stride,
+                             int64_t *d_start, int64_t *d_shift, double *d_score);
+/* the DFT alone at given per-stream (offset, shift): Y [n_streams][S][8][2];
+ * an offset outside [0, L - 1] or a shift outside [-search, search] is
+ * AMR_E_INVALID before any device work */
+int amr_tone8_symbols_at_host(amr_tone8_plan *plan, const void *x, int dtype, int64_t n_streams, int64_t x_stride,
+                              const int64_t *offset, const int64_t *shift, double *Y);
+/* the score and maximum stage alone on given window energies P
+ * [n_streams][n_win][15 + 2 search] (column li is line c2 - search + li): the
+ * start slots are j < n_win - 48; start = j* T; score may be NULL */
+int amr_tone8_peak_host(int64_t T, int64_t search, const double *P, int64_t n_streams, int64_t n_win, int64_t *start,
+                        int64_t *shift, double *score);
+/* the slicer and soft stages alone on given Y [n_streams][n_sym][8][2]: words
+ * [n_streams][max(1, ceil(3 n_sym / 32))] (MSB first), soft [n_streams][3 n_sym]
+ * (every bit from 0) */
+int amr_tone8_slice_host(const double *Y, int64_t n_streams, int64_t n_sym, uint32_t *words);
+int amr_tone8_soft_host(const double *Y, int64_t n_streams, int64_t n_sym, int8_t *soft);
+/* tone8_modulate: the integer phase p in units of 1 / (2 L) cycle, p_0 = 0,
+ * p_{k+1} = (p_k + L * inc_k) % (2 L), inc_k = c2 + 2 tone_k; sample i of symbol
+ * k is float32(Sn[(p_k + i * inc_k) % (2 L)]), Sn [2 L] the caller's sine table,
+ * so the output is the restatement's bit for bit.  A frame of an n_bytes
+ * payload is (7 + ceil(8 n_bytes / 3)) * L samples; out / pcm / n_out as
+ * amr_modulate_host. */
+int amr_tone8_modulate_host(int64_t L, int64_t c2, const double *Sn, const uint8_t *data, int64_t data_stride,
+                            const int64_t *n_bytes, int64_t n, float *out, int64_t out_stride, int64_t n_out,
+                            int16_t *pcm, int64_t pcm_stride);
+
 /* ---- benchmark / test input generator (no reference counterpart) ----------
  * d_out[s][i] = d_base[(s + row_offset) % n_base][i] + sigma * N(0,1), float32,
  * the deviate hashed from (seed, s, i): distinct noisy batches over the same
