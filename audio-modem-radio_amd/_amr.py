@@ -29,6 +29,24 @@ PSK_QPSK, PSK_BPSK, PSK_D8PSK = 0, 1, 2
 # 8-ary differential modem) has QPSK's design (design_psk)
 PSK_KINDS = {"qpsk": PSK_QPSK, "bpsk": PSK_BPSK, "d8psk": PSK_D8PSK}
 PSK_BITS = {"qpsk": 2, "bpsk": 1, "d8psk": 3}
+# the later kinds: "star16" (the two-ring 16-DAPSK modem; QPSK's
+# design too).  The host layer looks a kind up through psk_kind / psk_bits,
+# which know these and the three above
+PSK_STAR16 = 4
+PSK_KINDS_MORE = {"star16": PSK_STAR16}
+PSK_BITS_MORE = {"star16": 4}
+
+
+def psk_kind(kind: str) -> int:
+    """AMR_PSK_* of a demodulator's kind name (KeyError names an unknown one)."""
+    return PSK_KINDS_MORE[kind] if kind in PSK_KINDS_MORE else PSK_KINDS[kind]
+
+
+def psk_bits(kind: str) -> int:
+    """Bits per symbol of a demodulator's kind name."""
+    return PSK_BITS_MORE[kind] if kind in PSK_BITS_MORE else PSK_BITS[kind]
+
+
 T_NAMES = ["bandpass", "lowpass_fwd", "lowpass_bwd", "lowpass_exact", "sync_pack", "fec", "launch"]
 TF_NAMES = ["bandpass", "hilbert", "decide", "launch", "exact"]
 # amr_frame_rec (include/amr.h), 64 bytes
@@ -106,8 +124,9 @@ DSSS_MAX_C = 64
 # even and odd periodic autocorrelation within 4 of 16
 DSSS_CODE = [1, 0, 0, 0, 1, 0, 1, 1, 0, 1, 1, 0, 0, 0, 1, 1]
 
-TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK = 0, 1, 2, 3, 4
-TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL, "d8psk": TX_D8PSK}
+TX_BPSK, TX_QPSK, TX_FSK, TX_HELL, TX_D8PSK, TX_STAR16 = 0, 1, 2, 3, 4, 6
+TX_MODES = {"bpsk": TX_BPSK, "qpsk": TX_QPSK, "fsk": TX_FSK, "hell": TX_HELL, "d8psk": TX_D8PSK,
+            "star16": TX_STAR16}
 
 # AMR_HELL_ELEM_* (include/amr.h): the element types the Hellschreiber receiver reads
 HELL_PCM16 = 11
@@ -237,14 +256,15 @@ def modulate(mode: int, datas, baud, f0, f1=0.0, samp_rate=96000, n_out=None, pc
 def psk_slice(kind: str, sym: np.ndarray) -> np.ndarray:
     """The slicer stage alone on the GPU (K4a): sym [B][S] complex128 -> the
     decided bits [B][bits] as uint8 (modem.py:214-241 QPSK, :100-105 BPSK;
-    "d8psk": k_slice8's eight sectors, 3 bits per product)."""
+    "d8psk": k_slice8's eight sectors, 3 bits per product; "star16":
+    k_slice16's ring bit and tribit, 4 per product)."""
     require_gpu()
     sym = np.ascontiguousarray(np.atleast_2d(sym), np.complex128)
     B, S = sym.shape
-    nbits = max(0, (S - 1) * PSK_BITS[kind])
+    nbits = max(0, (S - 1) * psk_bits(kind))
     nw = max(1, (nbits + 31) // 32)
     words = np.zeros((B, nw), np.uint32)
-    check(lib().amr_psk_slice_host(PSK_KINDS[kind], ptr(sym), B, S, ptr(words)))
+    check(lib().amr_psk_slice_host(psk_kind(kind), ptr(sym), B, S, ptr(words)))
     bits = np.unpackbits(words.astype(">u4").view(np.uint8).reshape(B, -1), axis=1)
     return bits[:, :nbits]
 
@@ -622,10 +642,10 @@ def design_psk(kind: str, n: int, baud, carrier=3000.0, samp_rate=96000):
     Order of the reference's failure points is kept: band-pass design,
     band-pass filtfilt padlen check, low-pass design (modem.py:76-88 / 197-204)."""
     from scipy import signal
-    PSK_KINDS[kind]                                      # KeyError names an unknown kind
+    psk_kind(kind)                                       # KeyError names an unknown kind
     sps = int(samp_rate / baud)
     nyq = samp_rate / 2
-    if kind in ("qpsk", "d8psk"):
+    if kind in ("qpsk", "d8psk", "star16"):
         low = (carrier - baud * 1.5) / nyq
         high = (carrier + baud * 1.5) / nyq
         first = sps // 2
@@ -739,7 +759,7 @@ class PskPlan:
         h = ctypes.c_void_p()
         b, a, zi = self.bp
         bl, al, zil = self.lp
-        check(lib().amr_psk_plan_create(ctypes.byref(h), self.device, PSK_KINDS[kind],
+        check(lib().amr_psk_plan_create(ctypes.byref(h), self.device, psk_kind(kind),
                                         n, self.sps, self.first, ptr(b), ptr(a), ptr(zi), len(b),
                                         ptr(bl), ptr(al), ptr(zil), len(bl), ptr(lo4), self.max_streams))
         self.handle = h
@@ -1016,7 +1036,7 @@ def get_psk_plan(kind: str, n: int, baud, carrier, samp_rate, batch: int) -> Psk
     first = sps if kind == "bpsk" else sps // 2
 
     def estimate(m):
-        return max(0, int(lib().amr_psk_plan_bytes_estimate(PSK_KINDS[kind], int(n), sps, first, 9, 5, m)))
+        return max(0, int(lib().amr_psk_plan_bytes_estimate(psk_kind(kind), int(n), sps, first, 9, 5, m)))
     return plan_cache.get(key, need, lambda m: PskPlan(kind, n, baud, carrier, samp_rate, max_streams=m, device=dev),
                           estimate if sps >= 1 else None)
 
@@ -1899,9 +1919,9 @@ def psk_soft(kind: str, sym: np.ndarray) -> np.ndarray:
     require_gpu()
     sym = np.ascontiguousarray(np.atleast_2d(sym), np.complex128)
     B, S = sym.shape
-    nbits = max(0, (S - 1) * PSK_BITS[kind])
+    nbits = max(0, (S - 1) * psk_bits(kind))
     soft = np.zeros((B, nbits), np.int8)
-    check(lib().amr_psk_soft_host(PSK_KINDS[kind], ptr(sym), B, S, ptr(soft)))
+    check(lib().amr_psk_soft_host(psk_kind(kind), ptr(sym), B, S, ptr(soft)))
     return soft
 
 

@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libamr.so")
 LIB_ID = LIB + ".id"                      # source_hash() of the tree LIB was linked from
-SOURCES = ["psk_kernels.hip", "psk_lane_kernels.hip", "psk_split_kernels.hip", "psk_soft_kernels.hip", "psk8_kernels.hip", "util_kernels.hip", "fft_kernels.hip", "fsk_kernels.hip", "fsk_exact_kernels.hip", "pocketfft_kernels.hip", "frame_kernels.hip", "tx_kernels.hip",
+SOURCES = ["psk_kernels.hip", "psk_lane_kernels.hip", "psk_split_kernels.hip", "psk_soft_kernels.hip", "psk8_kernels.hip", "star16_kernels.hip", "util_kernels.hip", "fft_kernels.hip", "fsk_kernels.hip", "fsk_exact_kernels.hip", "pocketfft_kernels.hip", "frame_kernels.hip", "tx_kernels.hip",
            "hell_kernels.hip", "viterbi_kernels.hip", "rs_kernels.hip", "ofdm_kernels.hip", "ofdm_acq_kernels.hip", "dsss_kernels.hip", "dsss_acq_kernels.hip", "msk_kernels.hip", "msk_acq_kernels.hip", "tone8_kernels.hip", "tone8_acq_kernels.hip", "api.cpp", "tx_api.cpp", "hell_api.cpp",
            "viterbi_api.cpp", "rs_api.cpp", "ofdm_api.cpp", "dsss_api.cpp", "msk_api.cpp", "tone8_api.cpp", "fsk_api.cpp", "pocketfft_plan.cpp"]
 HEADERS = ["amr_internal.h", "psk_common.h", "fft.h", "api_common.h", "plan_core.h", "sym_plan.h", "tx_host.h", "env_switch.h", "dev_mem.h", "fsk_exact.h", "pocketfft.h", "pocketfft_dev.h",

@@ -16,7 +16,8 @@ constexpr int kWave = 64;
 constexpr int kMaxTaps = 16;
 
 enum DType : int { kF32 = 0, kF64 = 1, kI16 = 2 };
-enum PskKind : int { kQpsk = 0, kBpsk = 1, kD8psk = 2 };   // kD8psk: QPSK's front end, its own slicer (psk8_kernels.hip)
+// kD8psk, kStar16: QPSK's front end, their own slicers (psk8_kernels.hip, star16_kernels.hip); 3 stays unknown
+enum PskKind : int { kQpsk = 0, kBpsk = 1, kD8psk = 2, kStar16 = 4 };
 
 // One IIR section as scipy.signal.lfilter sees it (a[0] == 1).
 struct Iir {

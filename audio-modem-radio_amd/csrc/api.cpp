@@ -30,6 +30,8 @@ hipError_t launch_psk_slice(const PskBuffers&, const PskParams&, hipStream_t, bo
 hipError_t launch_psk_soft(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
 hipError_t launch_psk_slice8(const PskBuffers&, const PskParams&, hipStream_t, bool only_flagged = false);
 hipError_t launch_psk_soft8(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
+hipError_t launch_psk_slice16(const PskBuffers&, const PskParams&, hipStream_t, bool only_flagged = false);
+hipError_t launch_psk_soft16(const PskBuffers&, const PskParams&, int8_t*, int64_t, hipStream_t);
 hipError_t launch_psk_bandpass_lane(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 hipError_t launch_psk_bandpass_fixup(const PskBuffers&, const PskParams&, const Iir&, hipStream_t);
 bool psk_lane_fused(const PskBuffers&, const PskParams&);
@@ -293,13 +295,21 @@ struct LastCall {
   }
 };
 
-bool psk_kind_ok(int kind) { return kind == AMR_PSK_QPSK || kind == AMR_PSK_BPSK || kind == AMR_PSK_D8PSK; }
-int psk_bits_per_symbol(int kind) { return kind == AMR_PSK_D8PSK ? 3 : kind == AMR_PSK_QPSK ? 2 : 1; }
-// the slicer and the soft stage of the plan's kind (K4a / K4s, or d8psk's psk8_kernels.hip)
+bool psk_kind_ok(int kind) {
+  return kind == AMR_PSK_QPSK || kind == AMR_PSK_BPSK || kind == AMR_PSK_D8PSK || kind == AMR_PSK_STAR16;
+}
+int psk_bits_per_symbol(int kind) {
+  return kind == AMR_PSK_STAR16 ? 4 : kind == AMR_PSK_D8PSK ? 3 : kind == AMR_PSK_QPSK ? 2 : 1;
+}
+// d8psk and star16: QPSK's front end, a slicer and a soft stage of their own, never fused, never time-split
+bool psk_own_slicer(int kind) { return kind == kD8psk || kind == kStar16; }
+// the slicer and the soft stage of the plan's kind (K4a / K4s, d8psk's psk8_kernels.hip, star16's star16_kernels.hip)
 hipError_t psk_slice_kind(const PskBuffers& b, const PskParams& p, hipStream_t st, bool only_flagged = false) {
+  if (p.kind == kStar16) return launch_psk_slice16(b, p, st, only_flagged);
   return p.kind == kD8psk ? launch_psk_slice8(b, p, st, only_flagged) : launch_psk_slice(b, p, st, only_flagged);
 }
 hipError_t psk_soft_kind(const PskBuffers& b, const PskParams& p, int8_t* soft, int64_t stride, hipStream_t st) {
+  if (p.kind == kStar16) return launch_psk_soft16(b, p, soft, stride, st);
   return p.kind == kD8psk ? launch_psk_soft8(b, p, soft, stride, st) : launch_psk_soft(b, p, soft, stride, st);
 }
 
@@ -709,7 +719,7 @@ int amr_psk_split_bounds_host(amr_psk_plan* plan, const void* x, int dtype, int6
   if (B > plan->max_streams) return fail(AMR_E_CAPACITY, "batch exceeds plan max_streams");
   if (dtype_size(dtype) == 0 || x_stride < plan->p.n) return fail(AMR_E_INVALID, "bad dtype / x_stride");
   if (!plan->split_designed) split_design(plan);
-  if (!plan->split_ok || plan->p.n_sym < 2 || plan->p.kind == kD8psk)
+  if (!plan->split_ok || plan->p.n_sym < 2 || psk_own_slicer(plan->p.kind))
     return fail(AMR_E_INVALID, "no time-split layout for this plan");
   // KS5 launches no strict kernel without decision bits: nothing to copy back
   if (plan->p.n_bits < 1 || plan->p.n_words < 1)
@@ -1070,8 +1080,8 @@ int pick_layout(amr_psk_plan* pl, int64_t B, bool soft) {
   // the lane kernels are written for butter(4) band-pass / low-pass
   // coefficient shapes: 9 taps and a palindromic 5-tap low-pass
   if (layout == AMR_LAYOUT_LANE && !(pl->bp.nt == 9 && pl->p.lp_sym)) layout = AMR_LAYOUT_ROW;
-  // (a d8psk plan likewise: its eight decision boundaries have no margin test yet)
-  if (layout == AMR_LAYOUT_SPLIT && (soft || pl->p.kind == kD8psk)) layout = AMR_LAYOUT_ROW;
+  // (a d8psk or star16 plan likewise: their decision boundaries have no margin test yet)
+  if (layout == AMR_LAYOUT_SPLIT && (soft || psk_own_slicer(pl->p.kind))) layout = AMR_LAYOUT_ROW;
   if (layout == AMR_LAYOUT_SPLIT) {
     if (!pl->split_designed) split_design(pl);
     if (!pl->split_ok || B > 65535 || pl->p.n_sym < 2) layout = AMR_LAYOUT_ROW;
@@ -1100,7 +1110,7 @@ PskBuffers psk_buffers(amr_psk_plan* pl, const PskCall& c) {
   b.out_len = c.io.len;
   b.sync_idx = c.io.sync;
   b.edge = c.edge;
-  b.no_fuse = c.soft.ptr || pl->p.kind == kD8psk ? 1 : 0;   // (the fused slicers decide QPSK / BPSK only)
+  b.no_fuse = c.soft.ptr || psk_own_slicer(pl->p.kind) ? 1 : 0;   // (the fused slicers decide QPSK / BPSK only)
   return b;
 }
 

@@ -38,6 +38,7 @@ int64_t tx_symbols(int mode, int64_t nb) {
   if (mode == AMR_TX_BPSK) return 80 + 8 * nb;
   if (mode == AMR_TX_HELL) return 105 + 51 * nb;             // pixels: 70 + 51 per character + 35
   if (mode == AMR_TX_D8PSK) return 40 + (8 * nb + 2) / 3;    // ([0,0,0]*30 + [1,1,0]*10 + 8n bits, zero-padded) / 3
+  if (mode == AMR_TX_STAR16) return 40 + 2 * nb;             // ([0,0,0,0]*30 + [1,1,1,0]*10 + 8n bits) / 4
   return 8 * (4 + nb);
 }
 
@@ -45,7 +46,7 @@ int64_t tx_symbols(int mode, int64_t nb) {
 // the message set) when the reference raises for these parameters
 int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_out, TxParams* p) {
   if (mode != AMR_TX_BPSK && mode != AMR_TX_QPSK && mode != AMR_TX_FSK && mode != AMR_TX_HELL &&
-      mode != AMR_TX_D8PSK)
+      mode != AMR_TX_D8PSK && mode != AMR_TX_STAR16)
     return fail(AMR_E_INVALID, "unknown modulation mode");
   if (baud == 0.0) return fail(AMR_E_INVALID, "float division by zero");
   if (!std::isfinite(baud) || !std::isfinite(fs)) return fail(AMR_E_INVALID, "baud and sample_rate must be finite");
@@ -78,7 +79,10 @@ int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_o
     p->c1 = p->c0;
     // d8psk (no reference counterpart): an empty ramp is an envelope of ones, no symbol is an error
     if (mode == AMR_TX_D8PSK && p->sps < 1) return fail(AMR_E_INVALID, "d8psk: fewer than one sample per symbol");
-    if (mode != AMR_TX_D8PSK && p->sps > 0 && p->ramp == 0)  // envelope[-0:] = linspace(1, 0, 0)
+    // star16: a parabolic envelope at any sps >= 1, no ramp
+    if (mode == AMR_TX_STAR16 && p->sps < 1) return fail(AMR_E_INVALID, "star16: fewer than one sample per symbol");
+    if (mode == AMR_TX_STAR16) p->ramp = 0;
+    if (mode != AMR_TX_D8PSK && mode != AMR_TX_STAR16 && p->sps > 0 && p->ramp == 0)  // envelope[-0:] = linspace(1, 0, 0)
       return fail(AMR_E_INVALID, "could not broadcast input array from shape (0,) into shape (" +
                                      std::to_string(p->sps) + ",)");
   }
@@ -86,7 +90,11 @@ int tx_setup(int mode, double baud, double f0, double f1, double fs, int64_t n_o
   return AMR_OK;
 }
 
-int64_t work_bytes(const TxParams& p, int64_t n) { return (3 * p.sps + n * p.sym_stride) * 8 + 256; }
+// the tables, then per stream and symbol a phase (star16: a phase and a ring amplitude)
+int64_t work_bytes(const TxParams& p, int64_t n) {
+  const int64_t per_sym = p.mode == AMR_TX_STAR16 ? 2 : 1;
+  return (3 * p.sps + per_sym * n * p.sym_stride) * 8 + 256;
+}
 
 }  // namespace
 

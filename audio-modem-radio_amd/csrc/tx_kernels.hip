@@ -7,6 +7,7 @@
 //   wav_from_array  /root/reference/modem.py:360-368  int16(arr * 32767)
 //   hellschreiber_modulate  hellschreiber.py:109-152  (AMR_TX_HELL, below)
 //   d8psk_modulate  no reference counterpart          (AMR_TX_D8PSK, below)
+//   star16_modulate no reference counterpart          (AMR_TX_STAR16, below)
 //
 // Three launches per call:
 //   T0 k_tx_tables  the per-symbol tables the reference rebuilds per symbol:
@@ -370,6 +371,126 @@ static void launch_tx_d8psk(const TxParams& p, const uint8_t* data, int64_t stri
                        pcm, pcm_stride);
 }
 
+// ---- AMR_TX_STAR16: star16_modulate (amr.h) ----
+// The bits [0,0,0,0]*30 + [1,1,1,0]*10 + payload, four at a time (MSB first)
+// (a, b2, b1, b0): the low three are d8psk's tribit and step the phase as
+// tx_step8 does, a toggles the ring (outer, amplitude 1.0, before the first
+// symbol; inner 0.5).  One byte is two symbols, so there is no padding.
+//   T0 k_tx_env16    env[i] = 4.0 * (u * (1.0 - u)), u = (i + 0.5) / sps: one
+//                    division, one subtraction, two products (no add after a
+//                    multiply); replaces k_tx_tables, whose w and ramps star16
+//                    does not read.
+//   T1 k_tx_phase16  T1's pattern, lane per stream: phase and ring carried
+//                    sequentially, (phase, amplitude) stored as one 16-B pair
+//                    per symbol ([n_streams][sym_stride] double2: twice the
+//                    phases' bytes, amr_tx_work_bytes counts them).
+//   T2 k_tx_synth16  sin(((2 pi) f0) * (n / fs) + ph[k]) * (env[i] * A[k]), the
+//                    carrier in absolute time as k_tx_synth8's.
+__device__ __forceinline__ int64_t tx_symbols16(int64_t nb) { return 40 + 2 * nb; }
+
+__global__ __launch_bounds__(256) void k_tx_env16(TxParams p, double* __restrict__ env) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.sps) return;
+  const double u = ((double)i + 0.5) / (double)p.sps;
+  env[i] = 4.0 * (u * (1.0 - u));
+}
+
+__device__ __forceinline__ double2 tx_step16(uint32_t nib, double& ph, uint32_t& ring) {
+  ph = tx_step8(nib & 7u, ph);
+  ring ^= (nib >> 3) & 1u;
+  return make_double2(ph, ring ? 1.0 : 0.5);
+}
+
+__global__ __launch_bounds__(64) void k_tx_phase16(const uint8_t* __restrict__ data, int64_t stride,
+                                                   const int64_t* __restrict__ n_bytes, int64_t n_streams, TxParams p,
+                                                   double2* __restrict__ phase) {
+  const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+  if (s >= n_streams) return;
+  int64_t nb = n_bytes[s];
+  nb = nb < 0 ? 0 : (nb > stride ? stride : nb);
+  const uint8_t* __restrict__ d = data + s * stride;
+  const int64_t total = tx_symbols16(nb);
+  const int64_t n = total < p.sym_stride ? total : p.sym_stride;   // symbols stored
+  double2* __restrict__ out = phase + s * p.sym_stride;
+  double ph = 0.0;
+  uint32_t ring = 1u;                                // outer before the first symbol
+  int64_t j = 0;
+  for (; j < 40 && j < n; ++j) out[j] = tx_step16(j < 30 ? 0x0u : 0xEu, ph, ring);   // [0,0,0,0]*30 + [1,1,1,0]*10
+  for (int64_t q = 0; j < n; ++q, j += 2) {          // j = 40 + 2 q, q < nb: symbol j exists
+    const uint32_t byte = d[q];
+    const double2 hi = tx_step16(byte >> 4, ph, ring);
+    const double2 lo = tx_step16(byte & 15u, ph, ring);
+    out[j] = hi;
+    if (j + 1 < n) out[j + 1] = lo;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_tx_synth16(const int64_t* __restrict__ n_bytes, int64_t stride, TxParams p,
+                                                    const double2* __restrict__ phase, const double* __restrict__ env,
+                                                    float* __restrict__ out, int64_t out_stride,
+                                                    int16_t* __restrict__ pcm, int64_t pcm_stride) {
+  const int64_t s = blockIdx.y;
+  int64_t nb = n_bytes[s];
+  nb = nb < 0 ? 0 : (nb > stride ? stride : nb);
+  const int64_t len = tx_symbols16(nb) * p.sps;
+  const double2* __restrict__ ph = phase + s * p.sym_stride;
+  const uint32_t sps = (uint32_t)p.sps;
+  const int64_t k0 = (int64_t)blockIdx.x * 1024 + 4 * threadIdx.x;
+  if (k0 >= p.n_out) return;
+  uint32_t sym = (uint32_t)k0 / sps;
+  uint32_t i = (uint32_t)k0 - sym * sps;
+  float f[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    f[u] = 0.0f;
+    if (k0 + u < len && k0 + u < p.n_out) {
+      const double t = (double)(k0 + u) / p.fs;      // n / samp_rate
+      const double2 pa = ph[sym];                    // (phase, ring amplitude)
+      f[u] = (float)(sin(p.c0 * t + pa.x) * (env[i] * pa.y));
+    }
+    if (++i == sps) {
+      i = 0;
+      ++sym;
+    }
+  }
+  int16_t q[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) q[u] = (int16_t)(int)(f[u] * 32767.0f);   // (arr * 32767).astype(np.int16)
+  float* __restrict__ o = out + s * out_stride + k0;
+  int16_t* __restrict__ c = pcm ? pcm + s * pcm_stride + k0 : nullptr;
+  if (VEC && k0 + 4 <= p.n_out) {
+    *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
+    if (c) *reinterpret_cast<short4*>(c) = make_short4(q[0], q[1], q[2], q[3]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (k0 + u < p.n_out) {
+        o[u] = f[u];
+        if (c) c[u] = q[u];
+      }
+    }
+  }
+}
+
+// work: env [sps] (at the tables' env slot), then the (phase, amplitude) pairs
+static void launch_tx_star16(const TxParams& p, const uint8_t* data, int64_t stride, const int64_t* n_bytes,
+                             int64_t n_streams, double* env, double2* phase, float* out, int64_t out_stride,
+                             int16_t* pcm, int64_t pcm_stride, hipStream_t st) {
+  hipLaunchKernelGGL(k_tx_env16, dim3((unsigned)((p.sps + 255) / 256)), dim3(256), 0, st, p, env);
+  const dim3 pg((unsigned)((n_streams + kWave - 1) / kWave));
+  hipLaunchKernelGGL(k_tx_phase16, pg, dim3(kWave), 0, st, data, stride, n_bytes, n_streams, p, phase);
+  const dim3 sg((unsigned)((p.n_out + 1023) / 1024), (unsigned)n_streams);
+  const bool vec = (out_stride % 4) == 0 && ((uintptr_t)out % 16) == 0 &&
+                   (!pcm || ((pcm_stride % 4) == 0 && ((uintptr_t)pcm % 8) == 0));
+  if (vec)
+    hipLaunchKernelGGL((k_tx_synth16<true>), sg, dim3(256), 0, st, n_bytes, stride, p, phase, env, out, out_stride, pcm,
+                       pcm_stride);
+  else
+    hipLaunchKernelGGL((k_tx_synth16<false>), sg, dim3(256), 0, st, n_bytes, stride, p, phase, env, out, out_stride,
+                       pcm, pcm_stride);
+}
+
 // ---- AMR_TX_HELL: hellschreiber_modulate (hellschreiber.py:109-152) ----
 // The payload is one glyph index per character (0..94 = ' '..'~', kHellBlank
 // for a character outside the table: the host did the UTF-8 decode).  Pixels:
@@ -510,6 +631,11 @@ hipError_t launch_tx(const TxParams& p, const uint8_t* data, int64_t stride, con
   }
   double* tab = work;
   double* phase = work + ((3 * p.sps + 1) & ~(int64_t)1);   // 16-B aligned rows (sym_stride is even)
+  if (p.mode == AMR_TX_STAR16) {                            // its own env table, (phase, amplitude) pairs
+    launch_tx_star16(p, data, stride, n_bytes, n_streams, tab + 2 * p.sps, reinterpret_cast<double2*>(phase), out,
+                     out_stride, pcm, pcm_stride, st);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_tx_tables, dim3((unsigned)((p.sps + 255) / 256)), dim3(256), 0, st, p, tab);
   if (p.mode == AMR_TX_QPSK)
     launch_tx_mode<AMR_TX_QPSK>(p, data, stride, n_bytes, n_streams, tab, phase, out, out_stride, pcm, pcm_stride, st);

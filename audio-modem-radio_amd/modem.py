@@ -17,6 +17,11 @@ d8psk (no reference counterpart): a real 8-ary differential
 PSK modem, 3 bits per symbol, beside the psk8_* aliases the reference keeps:
   d8psk_modulate, d8psk_demodulate (+ _batch, _soft, _soft_batch).
 
+star16 (no reference counterpart): a real two-ring 16-DAPSK
+modem, 4 bits per symbol (a ring toggle and d8psk's tribit), beside the
+apsk16_modulate alias the reference keeps (a QPSK call):
+  star16_modulate, star16_demodulate (+ _batch, _soft, _soft_batch).
+
 ofdm (no reference counterpart): a real multi-carrier DQPSK
 modem beside the ofdm_*_simple aliases the reference keeps:
   ofdm_modulate, ofdm_demodulate (+ _batch, _soft, _soft_batch).
@@ -473,12 +478,52 @@ def tone8_acquire(samples, baud, carrier, samp_rate=96000, search=6):
     return int(start[0]), int(shift[0])
 
 
+# ---------------------------------------------------------------------------
+# star16: two-ring 16-ary differential amplitude and phase keying (DESIGN.md
+# §3o).  QPSK's front end, d8psk's tribit on the differential product and a
+# ring bit from the two symbols' energies; differential in both, so it needs no
+# gain control and no carrier phase reference.
+def star16_demodulate(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000) -> bytes:
+    """Two-ring 16-DAPSK demodulation of one stream, on the GPU."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("star16_demodulate expects a 1-D sample array (use star16_demodulate_batch)")
+    return _psk_batch("star16", x[None, :], baud, carrier, samp_rate)[0]
+
+
+def star16_demodulate_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000) -> list:
+    """[B, N] equal-length streams -> B bytes objects (each == star16_demodulate(row))."""
+    return _psk_batch("star16", np.asarray(samples), baud, carrier, samp_rate)
+
+
+def star16_demodulate_soft(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """star16_demodulate's bytes and their soft values: (bytes, int8 array of 8 * len(bytes)).
+    Four values per symbol, a, b2, b1, b0; a's magnitude is 64 at equal energies
+    and 51 at a clean ring change, b0's tops out near 74 as d8psk's."""
+    x = _as_batch(samples)
+    if x.ndim != 1:
+        raise ValueError("star16_demodulate_soft expects a 1-D sample array (use star16_demodulate_soft_batch)")
+    outs, softs = _psk_soft_batch("star16", x[None, :], baud, carrier, samp_rate)
+    return outs[0], softs[0]
+
+
+def star16_demodulate_soft_batch(samples: np.ndarray, baud=1200, carrier=3000.0, samp_rate=96000):
+    """[B, N] equal-length streams -> (B bytes objects, B int8 arrays)."""
+    return _psk_soft_batch("star16", np.asarray(samples), baud, carrier, samp_rate)
+
+
+def _pcm16_star16(pcm: np.ndarray, baud, carrier=3000.0, samp_rate=96000) -> bytes:
+    """16-bit WAV samples as pcm / 32768 (as _pcm16_psk): star16_demodulate of that capture."""
+    return _pcm16_psk("star16", pcm, baud, carrier, samp_rate)
+
+
 def demodulate_ragged(kind: str, streams, baud, carrier=3000.0, samp_rate=96000) -> list:
     """Ragged batch: streams of different lengths and dtypes, grouped by
     (length, dtype) on the host -- each result == <kind>_demodulate(stream):
     a stream keeps its own dtype (and with it its odd extension, _as_batch)
     rather than the one numpy would promote a mixed stack to."""
-    fn = {"qpsk": qpsk_demodulate_batch, "bpsk": bpsk_demodulate_batch, "d8psk": d8psk_demodulate_batch}[kind]
+    fn = {"qpsk": qpsk_demodulate_batch, "bpsk": bpsk_demodulate_batch, "d8psk": d8psk_demodulate_batch,
+          "star16": star16_demodulate_batch}[kind]
     rows = [_as_batch(s) for s in streams]
     groups: dict = {}
     for i, r in enumerate(rows):
@@ -642,6 +687,13 @@ def d8psk_modulate(data_bytes: bytes, baud=1200, carrier=3000.0, samp_rate=96000
     return _amr.modulate(_amr.TX_D8PSK, [bytes(data_bytes)], baud, carrier, 0.0, samp_rate)[0]
 
 
+def star16_modulate(data_bytes: bytes, baud=1200, carrier=3000.0, samp_rate=96000) -> np.ndarray:
+    """Two-ring 16-DAPSK: [0,0,0,0]*30 + [1,1,1,0]*10 + the payload's bits, four
+    per symbol: a ring toggle (amplitude 1.0 / 0.5) and d8psk's Gray-coded phase step, on a
+    phase-continuous carrier under a parabolic symbol envelope; 40 + 2 len symbols."""
+    return _amr.modulate(_amr.TX_STAR16, [bytes(data_bytes)], baud, carrier, 0.0, samp_rate)[0]
+
+
 def ofdm_modulate(data_bytes: bytes, baud, carrier, num_subcarriers, samp_rate=96000) -> np.ndarray:
     """Multi-carrier DQPSK: [0,0]*30 + [1,1]*10 + the payload's bits,
     zero-padded to a multiple of 2 K; dibit j on OFDM symbol 1 + j // K, subcarrier
@@ -677,7 +729,7 @@ def modulate_batch(kind: str, datas, baud=1200, f0=None, f1=None, samp_rate=9600
                    num_subcarriers=None, code=None):
     """Batched modulators: [B, n_out] float32 (each row == <kind>_modulate(datas[b])
     cut / zero-padded to n_out; default the longest), plus wav_from_array's
-    int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' | 'd8psk' (f0 = carrier) or
+    int16 samples when pcm=True.  kind: 'bpsk' | 'qpsk' | 'd8psk' | 'star16' (f0 = carrier) or
     'fsk' (f0 = mark_freq, f1 = space_freq), or 'hell' (datas: texts or UTF-8
     bytes, decoded as feld_hell_modulate does; f0 = carrier, default 1000;
     pass baud=122.5 for the reference's default), or 'ofdm' (f0 = carrier,

@@ -477,12 +477,13 @@ def demod_sharded(x, demod_batch, transport, cap: int | None = None, steps=None)
 
 
 def demodulate_sharded(kind: str, x: np.ndarray, baud, transport, **kw):
-    """modem.{qpsk,bpsk,d8psk,fsk}_demodulate_batch over the ranks: each rank
+    """modem.{qpsk,bpsk,d8psk,star16,fsk}_demodulate_batch over the ranks: each rank
     demodulates its shard of the global [B, N] batch on its GPU, the decoded
     bytes are all-gathered; every rank returns the global list[bytes]."""
     import modem
     fn = {"qpsk": modem.qpsk_demodulate_batch, "bpsk": modem.bpsk_demodulate_batch,
-          "d8psk": modem.d8psk_demodulate_batch, "fsk": modem.fsk_demodulate_batch}[kind]
+          "d8psk": modem.d8psk_demodulate_batch, "star16": modem.star16_demodulate_batch,
+          "fsk": modem.fsk_demodulate_batch}[kind]
     return demod_sharded(np.asarray(x), lambda xs: fn(xs, baud=baud, **kw), transport)
 
 

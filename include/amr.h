@@ -96,7 +96,10 @@ extern "C" {
                                   and a kind of amr_psk_slice_host / amr_psk_soft_host) and
                                   AMR_TX_D8PSK (a modulation mode); the multi-carrier DQPSK
                                   modem (amr_ofdm_*, AMR_TO_*); the direct-sequence DBPSK
-                                  modem (amr_dsss_*, AMR_TD_*) */
+                                  modem (amr_dsss_*, AMR_TD_*); the two-ring 16-DAPSK modem
+                                  star16: AMR_PSK_STAR16 (a plan kind, and a kind of
+                                  amr_psk_slice_host / amr_psk_soft_host) and AMR_TX_STAR16
+                                  (a modulation mode) */
 
 #define AMR_OK 0
 #define AMR_E_INVALID -1      /* bad argument */
@@ -124,6 +127,23 @@ extern "C" {
  * d8psk plan never runs the time-split layout (it takes the row layout
  * instead) and its lane layout always slices in a kernel of its own. */
 #define AMR_PSK_D8PSK 2
+/* star16: two-ring 16-ary differential amplitude and phase keying, 4 bits per
+ * symbol (a, b2, b1, b0) (no reference counterpart: the reference's "APSK16"
+ * is a QPSK alias).  QPSK's filters, sps and first symbol.
+ * b2 b1 b0 is d8psk's tribit of d = s[k+1] * conj(s[k]), unchanged.  With
+ * e = sr*sr + si*si of a symbol (two rounded products, one rounded sum):
+ *   a = (e[k+1] > 2.0 * e[k]) | (e[k] > 2.0 * e[k+1])      (the ring changed)
+ * -- false for NaN, inf against inf, zeros and exact ties.  The nibble 8 a + g
+ * goes out MSB first, 4 (S - 1) bits per stream, eight products per word; sync
+ * search and byte pack as for the others.  Soft values (amr_psk_demod_soft_*,
+ * amr_psk_soft_host): four per product, a's magnitude from
+ *   num = min(|e1 - 2.0 e0|, |e0 - 2.0 e1|), den = e0 + e1
+ * by the common rule, the other three d8psk's.  Both decisions compare like
+ * with like: a capture scaled by any power of two decodes to the same bits.
+ * As d8psk, a star16 plan never runs the time-split layout (it takes the row
+ * layout instead) and its lane layout always slices in a kernel of its own.
+ * (Kind 3 is not assigned.) */
+#define AMR_PSK_STAR16 4
 
 /* kernel timing slots reported by amr_psk_plan_timings() */
 #define AMR_T_BANDPASS 0
@@ -156,10 +176,10 @@ int amr_memcpy_d2d(void *dst, const void *src, int64_t bytes);
 int amr_device_synchronize(void);
 
 /* ---- DPSK demodulation ------------------------------------------------------
- * kind          AMR_PSK_QPSK | AMR_PSK_BPSK | AMR_PSK_D8PSK
+ * kind          AMR_PSK_QPSK | AMR_PSK_BPSK | AMR_PSK_D8PSK | AMR_PSK_STAR16
  * n_samples     samples per stream (all streams of a call share it)
  * sps           int(fs / baud)                                 modem.py:70,191
- * first_symbol  sps // 2 (QPSK, modem.py:209; d8psk) or sps (BPSK, modem.py:92)
+ * first_symbol  sps // 2 (QPSK, modem.py:209; d8psk, star16) or sps (BPSK, modem.py:92)
  * bp_*          band-pass b, a, lfilter_zi (ntaps each; a[0] must be 1)
  * lp_*          low-pass  b, a, lfilter_zi
  * lo4           [n_samples][4] doubles: lo_re, lo_im, -(0*lo_im), 0*lo_re
@@ -615,6 +635,17 @@ int amr_frame_parse_device(amr_psk_plan *plan, const uint8_t *d_in, int64_t in_s
  * PSK modulators' 10 % ramps, all ones when the ramp is empty (sps < 10 is
  * allowed); sps < 1 is AMR_E_INVALID. */
 #define AMR_TX_D8PSK 4
+/* star16_modulate (no reference counterpart): the bits
+ * [0,0,0,0]*30 + [1,1,1,0]*10 + payload, four at a time (MSB first)
+ * (a, b2, b1, b0): b2 b1 b0 steps the phase as d8psk's tribit does, a toggles
+ * the ring (outer before the first symbol; A = 1.0 outer, 0.5 inner);
+ * 40 + 2 n_bytes symbols of sps = int(sample_rate / baud) samples:
+ *   out[n] = float32(sin(((2 pi) f0) * (n / sample_rate) + phase[n / sps]) * (env[n % sps] * A[n / sps]))
+ *   env[i] = 4.0 * (u * (1.0 - u)),  u = (i + 0.5) / sps
+ * -- the carrier in absolute time, a parabolic envelope at any sps >= 1;
+ * sps < 1 is AMR_E_INVALID.  Its work buffer holds a phase and an amplitude
+ * per symbol (amr_tx_work_bytes).  (Mode 5 is not assigned.) */
+#define AMR_TX_STAR16 6
 /* natural waveform length of an n_bytes payload (the reference's len(out)), or < 0 */
 int64_t amr_tx_samples(int mode, int64_t n_bytes, double baud, double sample_rate);
 /* device scratch bytes amr_modulate_device needs for this shape */
